@@ -1,9 +1,13 @@
 #!/usr/bin/env python
 """Headline benchmark: audio-seconds synthesised per wall-second (1/RTF), CosyVoice2-0.5B zero-shot, batch 1, 10 CFM Euler steps
-(BASELINE.json configs[1]) on the synthetic U10 utterance of SURVEY.md §8d, plus first-chunk p50 latency in streaming mode.
+(BASELINE.json configs[1]) on the synthetic U10 utterance of SURVEY.md §8d; with `--full` also first-chunk p50 latency in streaming mode.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes what the last timed step computed if `--dump-outputs DIR` is given, and prints the result
+line.  `--full` adds everything else the line used to carry, after the timed region: the token self-checks against the oracle's files, the stage split,
+first-chunk latency, the other BASELINE.json configurations (extras, each in a process of its own), the roofline records and the CPU baseline.
 
 One process per GPU, each pinned to its GPU with HIP_VISIBLE_DEVICES before the first HIP call (inside a rank there is exactly one device, so
 no host thread of the pipeline can land on a neighbour's).  Utterances are independent, so ranks are replicas of the whole pipeline: no data-path collective,
@@ -843,13 +847,36 @@ def mixed_requests(cfgs, device, n=None):
     return reqs, costs
 
 
-def run_mixed(model, reqs, mine, slots=8):
-    """This rank's shard through the throughput pipeline (LM continuous batching overlapped with flow + HiFT); returns {index: sha1 of wav}."""
+def run_mixed(model, reqs, mine, slots=8, wavs=None):
+    """This rank's shard through the throughput pipeline (LM continuous batching overlapped with flow + HiFT); returns {index: sha1 of wav}
+    (`wavs`, a dict, receives {index: host waveform})."""
     import hashlib
     out = {}
     for j, res in model.tts_queue([reqs[i] for i in mine], slots=slots, order=os.environ.get("CV_BENCH_MIXED_ORDER", "longest_first")):      # (A/B knob: "fifo")
         out[mine[j]] = hashlib.sha1(res["tts_speech"].numpy().tobytes()).hexdigest()
+        if wavs is not None:
+            wavs[mine[j]] = res["tts_speech"]
     return out
+
+
+DUMP_SAMPLES_PER_UTTERANCE = 131072     # mixed64: 64 waveforms of up to 480 000 samples = 77 MB; a seeded sample of each keeps a dump at <= 32 MB
+
+
+def dump_outputs(path, last, rank):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as float32 / float64 .npy files.  U10: the waveform [1, 240000] and the 250
+    speech tokens (rank 0; every rank synthesises the same utterance).  mixed64: one file per utterance, written by the rank that synthesised it - the
+    whole waveform, or a fixed sample of DUMP_SAMPLES_PER_UTTERANCE samples (indices drawn with the utterance index as seed, kept in order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if "wavs" in last:
+        for i, wav in sorted(last["wavs"].items()):
+            w = wav.numpy().reshape(-1).astype(np.float32)
+            if w.size > DUMP_SAMPLES_PER_UTTERANCE:
+                w = w[np.sort(np.random.default_rng(i).choice(w.size, DUMP_SAMPLES_PER_UTTERANCE, replace=False))]
+            np.save(os.path.join(path, "mixed64_waveform_%02d.npy" % i), w)
+    elif rank == 0:
+        np.save(os.path.join(path, "waveform.npy"), last["wav"].numpy().astype(np.float32))
+        np.save(os.path.join(path, "speech_tokens.npy"), np.asarray([int(t) for t in last["tokens"]], dtype=np.float64))
 
 
 def check_mixed_tokens(tokens_by_index):
@@ -890,7 +917,7 @@ def check_mixed_tokens(tokens_by_index):
 
 
 def mixed64_extra(model, cfgs, lanes):
-    """BASELINE.json configs[3] on ONE GPU as an extra of the default line: the 64 mixed-length utterances through tts_queue (16 sequences in
+    """BASELINE.json configs[3] on ONE GPU as an extra of the --full line: the 64 mixed-length utterances through tts_queue (16 sequences in
     flight), one untimed pass then one timed pass; per-utterance waveform hashes and the token check against the oracle."""
     import hashlib
     reqs, costs = mixed_requests(cfgs, model.device)
@@ -1047,12 +1074,21 @@ def main():
     ap.add_argument("--hift-batch", action="store_true", help="extras only (A/B knob, off by default until measured): the equal-length members of a flow group share one "
                     "HiFT launch sequence in tts_batch / tts_queue (CosyVoice2Model.hift_batch, cv_hift_inference_batch; bit-identical per utterance)")
     ap.add_argument("--cv3-steps", type=int, default=4, help="CFM Euler steps of the --cv3 extra (configs[4] names 4; the reference hard-codes 10)")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1 only: skip the extra keys the default line carries next to `value` - `batched_decode` (8 and 16 "
+    ap.add_argument("--no-extras", action="store_true", help="N = 1 with --full only: skip the extra keys the --full line carries next to `value` - `batched_decode` (8 and 16 "
                     "sequences), `streaming_clients` (8 clients, 104 requests: BASELINE.json configs[2]), `mixed64` (configs[3] on one GPU), `cosyvoice3` (configs[4] shape) and `cosyvoice300m` "
                     "(CosyVoice-300M dimensions on the kernels, SURVEY 8 row f4) - each with its own token self-check; they add about four minutes")
+    ap.add_argument("--full", action="store_true", help="after the timed region, everything besides the headline: token self-checks (greedy and RAS against the "
+                    "oracle's files), stage split, first-chunk p50, the extras, the roofline records and the CPU baseline; the options above marked extra, "
+                    "--no-extras, --no-cpu-baseline and --first-chunk-reps apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64): "
+                    "U10 - waveform.npy and speech_tokens.npy; mixed64 - mixed64_waveform_<i>.npy per utterance (a seeded sample of a long one)")
     ap.add_argument("--cpu-stage", choices=CPU_STAGES, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--only-extra", choices=DEFAULT_EXTRAS, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and not args.only_extra and (args.batch or args.streams > 1 or args.stream_clients or args.cv3):
+        ap.error("--batch, --streams, --stream-clients and --cv3 are measured after the headline: add --full")
     if args.cpu_stage:
         cpu_stage(args.cpu_stage)
         return
@@ -1082,6 +1118,7 @@ def main():
     # the product path's host work is a few tiny CPU tensor ops per utterance: keep torch's intra-op pool small so that N ranks on
     # one node do not oversubscribe the host (cpu_baseline() sets its own thread count for the oracle run)
     torch.set_num_threads(max(1, min(8, (os.cpu_count() or 8) // max(world, 1))))
+    torch.manual_seed(0)                                       # the same inputs run to run, whatever draws from the global generator
     dist = None
     if world > 1:
         import torch.distributed as dist
@@ -1093,19 +1130,21 @@ def main():
     model.flow_batch = args.flow_batch
     log("model built")
     mixed = None
+    last = {}                                                    # what the latest step handed back (--dump-outputs)
     if args.workload == "mixed64":
         from cosyvoice_amd.replica import shard_requests
         reqs, costs = mixed_requests(cfgs, model.device)
         mine = shard_requests(costs, world)[rank]
         mixed = {"hashes": {}}
         if not DRY:
-            model.set_lanes(args.lanes)                          # the throughput pipeline's token2wav lanes (what the mixed64 extra of the default line runs with: --lanes, default 2)
+            model.set_lanes(args.lanes)                          # the throughput pipeline's token2wav lanes (what the mixed64 extra of the --full line runs with: --lanes, default 2)
 
         def step():
-            mixed["hashes"] = run_mixed(model, reqs, mine, slots=max(1, min(2 if DRY else 48, len(mine))))      # 8 in flight per GPU at 8 GPUs, 48 (three chains of 16) when one GPU takes all 64
+            last["wavs"] = {}
+            mixed["hashes"] = run_mixed(model, reqs, mine, slots=max(1, min(2 if DRY else 48, len(mine))), wavs=last["wavs"])      # 8 in flight per GPU at 8 GPUs, 48 (three chains of 16) when one GPU takes all 64
     else:
         def step():
-            one_utterance(model, u)
+            last["wav"] = one_utterance(model, u, last)
     for _ in range(args.warmup):
         step()
     log("warmup done")
@@ -1143,6 +1182,8 @@ def main():
                     all_hashes.update(d)
         else:
             all_hashes = mixed["hashes"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank)
     if rank == 0:
         value = world * args.steps * AUDIO_S / elapsed
         if mixed is not None:
@@ -1175,11 +1216,14 @@ def main():
             out["config"]["lanes"] = None if DRY else args.lanes
             # identical at every rank count / batch slot when the determinism contract of SURVEY.md section 8e holds
             out["utterance_hashes_sha1"] = hashlib.sha1("".join(all_hashes[i] for i in range(len(costs))).encode()).hexdigest()
+        if not args.full:
+            print(json.dumps(out), file=line_out, flush=True)
+    if rank == 0 and args.full:
         out["self_check"] = self_check(model, u)                 # U10 through the same model object, whatever the workload
         log("self-check passed: %s" % out["self_check"])
         if DRY:
             print(json.dumps(out), file=line_out, flush=True)
-    if rank == 0 and not DRY:                                    # everything below needs the full-size fixtures or the hardware
+    if rank == 0 and args.full and not DRY:                      # everything below needs the full-size fixtures or the hardware
         out["self_check"]["ras"] = ras_check(model, u)           # ... and a sampled, non-degenerate sequence of the same utterance
         log("RAS check passed: %s" % out["self_check"]["ras"])
         if world == 1 and args.workload == "u10":

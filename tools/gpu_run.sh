@@ -4,7 +4,7 @@
 # Every plan writes its logs under gpurun_out/<tag>/ and prints one summary line per step.  Plans:
 #   tests [pytest args]   the -m gpu suite (or the files / -k expression given in PYTEST_ARGS)
 #   smoke                 __graft_entry__.smoke()
-#   bench                 the driver's bench command (all extras)
+#   bench                 bench.py --full: the headline line with every check and extra
 #   extra:<name>[:ENV=V,ENV=V...]   one bench extra in a process of its own with A/B knobs in its environment
 #   prof:<name>           rocprofv3 --kernel-trace --stats of one bench extra -> kernel stats csv
 #   profbench             rocprofv3 --kernel-trace --stats of the bench command without extras
@@ -24,12 +24,12 @@ for plan in "$@"; do
   case "$plan" in
     tests)     run pytest_gpu 1200 python -X faulthandler -m pytest ${PYTEST_ARGS:-tests} -q -m gpu -p no:cacheprovider --timeout 500 ;;
     smoke)     run smoke 120 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)     run bench_driver 1200 python bench.py --gpus 1 --steps 20 --warmup 5
+    bench)     run bench_driver 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full
                python tools/bench_summary.py $O/bench_driver.log $O/bench_driver.json ;;
     extra:*)   IFS=: read -r _ name envs <<< "$plan"; envs=${envs#:}; tagname=$(echo "${name}_${envs:-default}" | tr -c 'A-Za-z0-9_\n' '_')
                ( for kv in $(echo "${envs:-}" | tr ',' ' '); do export "$kv"; done; run extra_$tagname 900 python bench.py --only-extra $name --steps $STEPS ) ;;
     prof:*)    IFS=: read -r _ name envs <<< "$plan"; envs=${envs#:}; ( for kv in $(echo "${envs:-}" | tr ',' ' '); do export "$kv"; done; prof $name python $R/bench.py --only-extra $name --steps 2 ) ;;
-    profbench) prof bench python $R/bench.py --gpus 1 --steps 5 --warmup 2 --no-extras --no-cpu-baseline ;;
+    profbench) prof bench python $R/bench.py --gpus 1 --steps 5 --warmup 2 --full --no-extras --no-cpu-baseline ;;
     pmcgemv)   ( cd /tmp && export TMPDIR=/tmp && timeout -k 5 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/$O/pmc_llm -- python $R/tools/profile_small.py llm > $R/$O/pmc_llm.log 2>&1; echo "== pmc llm rc=$?" )
                python tools/pmc_summary.py $O/pmc_gemv_fetch.json $O/pmc_llm -- gemv | head -12; rm -rf $O/pmc_llm ;;
     pmcflow)   ( cd /tmp && export TMPDIR=/tmp && timeout -k 5 200 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $R/$O/pmc_fb8_sq -- python $R/tools/profile_flow_batch.py 8 > $R/$O/pmc_fb8_sq.log 2>&1; echo "== pmc flow batch 8 sq rc=$?" )
