@@ -691,6 +691,12 @@ static void flow_tail(const TBlockW& t, const TBlockW* next, const bf16_t* att, 
     } else throw Error("flow_tail: no instantiation for these dimensions");
 }
 #endif
+// The launch of attn_flow32_kernel (flow_attn32.h) for `waves` = 2 | 4 waves per workgroup (64- or 128-query workgroups): its production grid and instantiations,
+// shared by the estimator (attn_flow) and the kernel's test entry point (cv_flow_attention_bf16).
+static void attn_flow32_launch(const AttnFlowArgs& a, int waves, hipStream_t s) {
+    if (waves == 2) hipLaunchKernelGGL((attn_flow32_kernel<2, 3>), dim3((unsigned)(((a.T + 63) / 64) * a.H * a.B)), dim3(128), 0, s, a);
+    else hipLaunchKernelGGL((attn_flow32_kernel<4, 3>), dim3((unsigned)(((a.T + 127) / 128) * a.H * a.B)), dim3(256), 0, s, a);
+}
 static void attn_flow(const bf16_t* qk, int ld, int inner, const bf16_t* vt, long long vt_batch, int ldt, bf16_t* o, int B, int H, int T, int chunk, hipStream_t s, const int* klen = nullptr,
                       bool big = false) {
     AttnFlowArgs a{};
@@ -701,10 +707,7 @@ static void attn_flow(const bf16_t* qk, int ld, int inner, const bf16_t* vt, lon
     if (tl_attn32) {
         // 128 queries per workgroup (4 waves).  64 (2 waves; option "attn32_waves" = 2) fill more CUs for a single utterance (176 instead of 96 workgroups at T = 674) and
         // measured SLOWER: 39.2 vs 37.5 ms per flow.inference (tools/probe_flow_r6b.py) - each K / V tile then serves half the queries.  Same bits either way.
-        const unsigned g128 = (unsigned)(((T + 127) / 128) * H * B);
-        const int nw = tl_attn32_waves == 2 ? 2 : 4;
-        if (nw == 2) hipLaunchKernelGGL((attn_flow32_kernel<2, 3>), dim3((unsigned)(((T + 63) / 64) * H * B)), dim3(128), 0, s, a);
-        else hipLaunchKernelGGL((attn_flow32_kernel<4, 3>), dim3(g128), dim3(256), 0, s, a);
+        attn_flow32_launch(a, tl_attn32_waves == 2 ? 2 : 4, s);
         return;
     }
 #ifdef CV_BUILD_EXPERIMENTS      // attn_flow_kernel (flow_fused.h), the attention of rounds 2-5 in its workgroup shapes: superseded by attn_flow32_kernel, kept for A/B builds (option attn32 = 0)
@@ -1293,6 +1296,27 @@ static void flow_profile_block(cv_flow* m, int nz, int T, int reps, float* us3, 
 }
 int cv_flow_profile_block(cv_flow* m, int32_t nz, int32_t T, int32_t reps, float* us3, void* stream) {
     return guarded([&] { CV_CHECK(m, "cv_flow_profile_block: null handle"); flow_profile_block(m, nz, T, reps, us3, as_stream(stream)); });
+}
+int cv_flow_attention_bf16(const void* q, const void* k, int32_t ld, const void* vt, int64_t vt_batch, int32_t ldt, void* o, int32_t ldo, int32_t B, int32_t H, int32_t T,
+                           float scale, int32_t chunk, const int32_t* klen, int32_t waves, void* stream) {
+    return guarded([&] {
+        CV_CHECK(q && k && vt && o, "cv_flow_attention_bf16: null operand");
+        CV_CHECK(B >= 1 && H >= 1 && T >= 1, "cv_flow_attention_bf16: bad shape");
+        CV_CHECK(ld % 8 == 0 && ld >= 64 * H, "cv_flow_attention_bf16: bad ld (a multiple of 8 bf16, at least 64 H)");
+        CV_CHECK(ldo % 4 == 0 && ldo >= 64 * H, "cv_flow_attention_bf16: bad ldo (a multiple of 4 bf16, at least 64 H)");
+        CV_CHECK(ldt % 64 == 0 && ldt >= (T + 63) / 64 * 64, "cv_flow_attention_bf16: bad ldt (a multiple of 64, at least T rounded up to 64)");
+        CV_CHECK(vt_batch >= 64LL * H * ldt, "cv_flow_attention_bf16: bad vt_batch (at least 64 H ldt)");
+        CV_CHECK(aligned16(q) && aligned16(k) && aligned16(vt) && (reinterpret_cast<uintptr_t>(o) & 7) == 0, "cv_flow_attention_bf16: unaligned operand (16 B q / k / vt, 8 B o)");
+        CV_CHECK(std::isfinite(scale) && scale > 0.f, "cv_flow_attention_bf16: bad scale (finite and positive)");
+        CV_CHECK(chunk >= 0, "cv_flow_attention_bf16: bad chunk");
+        CV_CHECK(waves == 0 || waves == 2 || waves == 4, "cv_flow_attention_bf16: bad waves (0, 2 or 4)");
+        AttnFlowArgs a{};
+        a.q = static_cast<const bf16_t*>(q); a.k = static_cast<const bf16_t*>(k); a.ld = ld;
+        a.vt = static_cast<const bf16_t*>(vt); a.vt_batch = vt_batch; a.ldt = ldt; a.o = static_cast<bf16_t*>(o); a.ldo = ldo;
+        a.B = B; a.H = H; a.T = T; a.scale = scale; a.mask_mode = chunk > 0 ? MASK_CHUNK : MASK_NONE; a.chunk = chunk; a.klen = klen; a.dbg = nullptr;
+        attn_flow32_launch(a, waves == 2 ? 2 : 4, as_stream(stream));
+        CV_HIP(hipGetLastError());
+    });
 }
 int cv_flow_estimator(cv_flow* m, const float* x, const float* mask, const float* mu, const float* t, const float* spks, const float* cond,
                       int32_t T, int32_t streaming, float* out, void* stream) {

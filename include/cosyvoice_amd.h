@@ -212,6 +212,15 @@ void cv_flow_destroy(cv_flow* m);
  * block of a LARGE pass - nz estimator batch rows (2 per utterance) of T frames - each timed as `reps` back-to-back launches between one HIP-event pair on `stream`;
  * us3[0..2] = microseconds per launch.  bf16 mode, U-Net estimator only. */
 int cv_flow_profile_block(cv_flow* m, int32_t nz, int32_t T, int32_t reps, float* us3, void* stream);
+/* test hook (no reference counterpart): the bf16-mode flash attention of the estimator's transformer blocks (csrc/flow_attn32.h), launched exactly as a pass launches it.
+ * q, k: dev bf16 [B * T][ld], head h at columns [64 h, 64 h + 64); vt: dev bf16 [B][H * 64][ldt], batch pitch vt_batch elements, row 64 h + d = V[:, h, d] with key t at
+ * column vt_col(t) (csrc/flow_fused.h: the key-permuted layout the QKV epilogues write); o: dev bf16 [B * T][ldo], columns [64 h, 64 h + 64) written for rows < B * T.
+ * chunk > 0: query t sees keys < (t / chunk + 1) chunk; klen: optional dev int32 [B], values 0 .. T, batch row b sees keys < klen[b] (0: an all-zero output row).
+ * waves: 0 (the estimator's default) | 2 | 4 waves per workgroup - the same bits.  Precondition the kernel cannot check: V^T columns [T, ldt) are finite (their
+ * probabilities are exactly 0, and 0 x finite = 0).  Refused with a message: null operands, B / H / T < 1, ld % 8 or ld < 64 H, ldo % 4 or ldo < 64 H, ldt % 64 or
+ * ldt < T rounded up to 64, vt_batch < 64 H ldt, q / k / vt not 16-byte or o not 8-byte aligned, scale not finite and positive, chunk < 0, waves not 0 / 2 / 4. */
+int cv_flow_attention_bf16(const void* q, const void* k, int32_t ld, const void* vt, int64_t vt_batch, int32_t ldt, void* o, int32_t ldo, int32_t B, int32_t H, int32_t T,
+                           float scale, int32_t chunk, const int32_t* klen, int32_t waves, void* stream);
 /* B4: flow.encoder(token_emb[1,n,dim], token_len, context=[1,3,dim] or empty, streaming) -> h[1,2n,dim]
  * (cosyvoice/flow/flow.py:258-261, transformer/upsample_encoder.py:244-307).  tok_emb / context / h_out: dev fp32, row-major. */
 int cv_flow_encoder(cv_flow* m, const float* tok_emb, int32_t n_tok, const float* context, int32_t streaming, float* h_out, void* stream);

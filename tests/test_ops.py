@@ -385,3 +385,99 @@ def test_attention_key_counts_per_batch_row(lib, bf16, mode, chunk):
         _sync(lib)
         assert torch.equal(got[b, :n].cpu(), alone[0].cpu())
         assert bool(torch.isfinite(got[b]).all())
+
+
+# ---- peaky scores against a float64 reference (the constructions of test_flow_attention.py): attention_kernel (fp32) and attention_bf16_kernel (variants 2, 3)
+
+def _attn64(q, k, v, scale, chunk, klen):
+    """float64 attention with the klen / chunk mask -> (out [B, T, H, 64], vmax [B, T, H] = max |v| over the keys a query sees)."""
+    B, T, H, _ = q.shape
+    out = torch.zeros(B, T, H, 64, dtype=torch.float64); vmax = torch.zeros(B, T, H, dtype=torch.float64)
+    i, j = torch.arange(T)[:, None], torch.arange(T)[None, :]
+    for b in range(B):
+        vis = j < klen[b]
+        if chunk > 0:
+            vis = vis & (j < (i // chunk + 1) * chunk)
+        s = (torch.einsum("qhd,khd->hqk", q[b].double(), k[b].double()) * scale).masked_fill(~vis[None], float("-inf"))
+        out[b] = torch.einsum("hqk,khd->qhd", torch.softmax(s, -1), v[b].double())
+        vmax[b] = torch.where(vis[:, :, None], v[b].double().abs().amax(-1)[None], torch.zeros(())).amax(1)
+    return out, vmax
+
+
+def _check_attn64(out, q, k, v, scale, chunk, klen, bf16):
+    """bf16 (q, k, v already rounded to bf16, the kernel's exact operands): P is rounded to bf16 for P.V (relative 2^-8 per probability) while the
+    denominator sums the unrounded P, the output stays fp32 -> |o - ref| <= 2^-8 vmax (1 + 2^-5).  fp32: a score is a 64-term fp32 dot product, absolute
+    error <= 64 2^-24 scale max sum_d |q_d k_d| = delta, which moves every probability by a relative exp(2 delta) - 1 ~ 2 delta, then fp32 rounding of the sums:
+    |o - ref| <= (2 delta + 2^-18) (vmax + |ref|)."""
+    ref, vmax = _attn64(q, k, v, scale, chunk, klen)
+    err = (out.cpu().double() - ref).abs()
+    if bf16:
+        bound = 2.0 ** -8 * vmax[..., None] * (1 + 2.0 ** -5)
+    else:
+        delta = 64 * 2.0 ** -24 * scale * torch.einsum("bqhd,bkhd->bhqk", q.abs().double(), k.abs().double()).max().item()
+        bound = (2 * delta + 2.0 ** -18) * (vmax[..., None] + ref.abs())
+    assert bool((err <= bound).all()), (err.max().item(), (err / bound).max().item())
+
+
+def _growing_keys(B, T, H, seed):
+    """Scores along one direction: q = (8 sigma, noise), k = (level / 8, noise), sigma alternating query by query.  Levels: tile 0 (keys 0-63) at 0, then a plateau
+    at 44 with a spike of 48 in tile 1 and one of 96 in tile 3 - the running maximum of a sigma = +1 query jumps twice after tile 0 while plateau keys from
+    before the second jump keep ~14 % of the weight (V mean +2 on tiles 1-2, -2 after them): a rescale that forgets the denominator, the accumulators or
+    the new maximum is off by a large fraction of vmax.  sigma = -1 queries see the mirror image (their maximum never moves after tile 0)."""
+    g = torch.Generator().manual_seed(seed)
+    q = torch.randn(B, T, H, 64, generator=g) * 0.2; k = torch.randn(B, T, H, 64, generator=g) * 0.2; v = torch.randn(B, T, H, 64, generator=g) * 0.5
+    levels = torch.full((T,), 44.0); levels[:64] = 0.0; levels[64 + 5] = 48.0; levels[192 + 17] = 96.0
+    q[..., 0] = 8.0 * (1.0 - 2.0 * (torch.arange(T) % 2).float())[None, :, None]
+    k[..., 0] = (levels / 8.0)[None, :, None]
+    v[:, 64:192] += 2.0; v[:, 192:] -= 2.0
+    return q, k, v
+
+
+@pytest.mark.parametrize("bf16", [False, 2, 3])
+@pytest.mark.parametrize("chunk", [0, 100])
+def test_attention_growing_key_norms_fp64(lib, bf16, chunk):
+    """attention_kernel / attention_bf16_kernel (the conformer encoder, the CosyVoice3 DiT, prefill) on scores whose running maximum jumps by ~50 raw units twice
+    after the first key tile (random inputs give a spread of ~8): the online-softmax rescale with live accumulators, against float64, with klen and the chunk mask."""
+    dev = _dev(lib)
+    B, T, H = 2, 320, 2
+    q, k, v = _growing_keys(B, T, H, 71)
+    if bf16:
+        q, k, v = q.bfloat16().float(), k.bfloat16().float(), v.bfloat16().float()
+    klen = [T, 250]
+    kl = lib.hook(torch.tensor(klen, dtype=torch.int32).to(dev))
+    out = ops.attention(lib, lib.hook(q.to(dev)), lib.hook(k.to(dev)), lib.hook(v.to(dev)), scale=0.125, mask="chunk" if chunk else "none", chunk=chunk, bf16=bf16, klen=kl)
+    _sync(lib)
+    _check_attn64(out, q, k, v, 0.125, chunk, klen, bf16)
+
+
+@pytest.mark.parametrize("bf16", [False, 2, 3])
+@pytest.mark.parametrize("chunk", [0, 13, 50])
+def test_attention_dominant_masked_keys_fp64(lib, bf16, chunk):
+    """Masked keys that would dominate if seen: K rows at or past klen[b] score +200 against every query (V there 3e4) - the output bits equal those of a launch
+    with zeros there; chunk edges: the first and the last key of every chunk score +22 (x16 weight) with V = +3 / -3, so a query that sees one key past its chunk or
+    misses its chunk's last one is off by far more than the float64 bound.  klen 150 / 97 / 33 / 1 (T = 150), chunks 13 (several boundaries per 64-query workgroup) and 50."""
+    dev = _dev(lib)
+    B, T, H = 4, 150, 2
+    klen = [150, 97, 33, 1]
+    g = torch.Generator().manual_seed(72 + chunk)
+    q = torch.randn(B, T, H, 64, generator=g) * 0.5; k = torch.randn(B, T, H, 64, generator=g) * 0.5; v = torch.randn(B, T, H, 64, generator=g)
+    q[..., 0] = 1.0
+    j = torch.arange(T)
+    c = chunk if chunk > 0 else T
+    first, last = (j % c == 0), (j % c == c - 1)
+    k[:, first, :, 0] = 22.0; k[:, last, :, 0] = 22.0
+    v[:, first] = 3.0 + 0.1 * v[:, first]; v[:, last] = -3.0 + 0.1 * v[:, last]
+    kz, vz, kf, vf = k.clone(), v.clone(), k.clone(), v.clone()
+    for b, n in enumerate(klen):
+        kz[b, n:] = 0.0; vz[b, n:] = 0.0
+        kf[b, n:] = 4.0; kf[b, n:, :, 0] = 200.0; vf[b, n:] = 3.0e4
+    if bf16:
+        q, kz, vz, kf, vf = (t.bfloat16().float() for t in (q, kz, vz, kf, vf))
+    kl = lib.hook(torch.tensor(klen, dtype=torch.int32).to(dev))
+    mode = "chunk" if chunk else "none"
+    outs = []
+    for kk, vv in ((kf, vf), (kz, vz)):
+        outs.append(ops.attention(lib, lib.hook(q.to(dev)), lib.hook(kk.to(dev)), lib.hook(vv.to(dev)), scale=0.125, mask=mode, chunk=chunk, bf16=bf16, klen=kl))
+        _sync(lib)
+    assert torch.equal(outs[0].cpu(), outs[1].cpu()), "masked keys changed the output"
+    _check_attn64(outs[1], q, kz, vz, 0.125, chunk, klen, bf16)
