@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include "ops.h"
 #include "tensor_map.h"
+#include "options.h"
 #include "flow_kernels.h"
 #include "flow_fused.h"
 #include "flow_attn32.h"
@@ -42,16 +43,6 @@ struct UStageW { int kind = 1, post = 0; Lin post_lin; };
 inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
-
-// Options that select a measured no-go (kept as evidence, built only with -DCV_BUILD_EXPERIMENTS: VERDICT r5 item 9)
-#ifdef CV_BUILD_EXPERIMENTS
-static constexpr bool kExperiments = true;
-#else
-static constexpr bool kExperiments = false;
-#endif
-static void need_experiments(bool wanted, const char* what) {
-    if (wanted && !kExperiments) throw Error(std::string(what) + " selects an experiment this library was built without (rebuild with CV_BUILD_EXPERIMENTS=1)");
-}
 
 struct cv_flow {
     cv_flow_config cfg{};
@@ -131,7 +122,7 @@ struct cv_flow {
     DevBuf klen; std::vector<int> host_klen; const int* cur_klen = nullptr;
     // hipGraph cache of the whole Euler solve, keyed by (T, n_steps, streaming): ~5000 launches per utterance become one replay.
     // A key is captured the second time it is seen (streaming requests change T every chunk and would only pay the instantiation).
-    bool use_graph = true;
+    int use_graph = 1;
     int graph_max_rows = 1000;         // "graph_max_rows": passes of at least this many estimator rows (2 x utterances x T) are not captured (0 = capture everything); CV_FLOW_GRAPH_MAX_ROWS.
                                        // 3000 until round 6; 1000 since: at 1348 rows (one utterance of U10) the launches average 9 us against the host's ~4 us per launch, the host stays
                                        // ahead and replaying the 3640-node graph costs more than issuing it - flow.inference 36.3 -> 34.9 ms, the bench 177.3 -> 176.0 ms per U10; the
@@ -167,6 +158,44 @@ struct cv_flow {
         if (side_stream) (void)hipStreamDestroy(side_stream);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
+};
+
+// One row per integer option: what cv_flow_set_option accepts by name and flow_finalize from the environment (options.h).  What an option does and what it
+// measured is written on its member above.  Not here: gemm_dbg, attn_dbg (they own a buffer) and graph_cap (a size_t), written out in cv_flow_set_option.
+using FlowOption = Option<cv_flow>;
+static const FlowOption kFlowOptions[] = {
+    // name             environment                 member                      bool   lo  hi       values               product    drops graphs
+    {"use_graph",       nullptr,                    &cv_flow::use_graph,        true,  0,  0,       0, {},               kAnyBuild, true},
+    {"bf16_mfma",       nullptr,                    &cv_flow::bf16_mfma,        true,  0,  0,       0, {},               kAnyBuild, true},
+    {"fused",           nullptr,                    &cv_flow::fused,            true,  0,  0,       0, {},               kAnyBuild, true},
+    {"flow_tile",       nullptr,                    &cv_flow::flow_tile,        false, 0,  4,       0, {},               kAnyBuild, true},
+    {"flow_ntile",      "CV_FLOW_NTILE",            &cv_flow::flow_ntile,       false, 0,  2,       0, {},               kAnyBuild, true},
+    {"res_tile",        "CV_FLOW_RES_TILE",         &cv_flow::res_tile,         false, 0,  1,       0, {},               kAnyBuild, true},
+    {"attn32",          "CV_FLOW_ATTN32",           &cv_flow::attn32,           true,  0,  0,       0, {},               1,         true},
+    {"attn32_waves",    "CV_FLOW_ATTN32_WAVES",     &cv_flow::attn32_waves,     false, 0,  0,       3, {0, 2, 4},        kAnyBuild, true},
+    {"attn_waves",      nullptr,                    &cv_flow::attn_waves,       false, 0,  0,       2, {2, 4},           kAnyBuild, true},
+    {"attn_kt",         nullptr,                    &cv_flow::attn_kt,          false, 1,  2,       0, {},               kAnyBuild, true},
+    {"attn_ks",         nullptr,                    &cv_flow::attn_ks,          false, 1,  4,       0, {},               kAnyBuild, true},
+    {"attn2_rows",      "CV_FLOW_ATTN2_ROWS",       &cv_flow::attn2_rows,       false, 0,  INT_MAX, 0, {},               kAnyBuild, true},
+    {"big_rows",        "CV_FLOW_BIG_ROWS",         &cv_flow::big_rows,         false, 0,  INT_MAX, 0, {},               kAnyBuild, true},
+    {"big_tile0",       "CV_FLOW_BIG_TILE0",        &cv_flow::big_tile0,        false, 0,  4,       0, {},               kAnyBuild, true},
+    {"big_tile1",       "CV_FLOW_BIG_TILE1",        &cv_flow::big_tile1,        false, 0,  4,       0, {},               kAnyBuild, true},
+    {"big_persist",     "CV_FLOW_BIG_PERSIST",      &cv_flow::big_persist,      false, -1, 8,       0, {},               kAnyBuild, true},
+    {"big_grid_cap",    nullptr,                    &cv_flow::big_grid_cap,     false, 0,  INT_MAX, 0, {},               kAnyBuild, true},
+    {"big_glds",        "CV_FLOW_BIG_GLDS",         &cv_flow::big_glds,         true,  0,  0,       0, {},               kAnyBuild, true},
+    {"big_lds_epi",     "CV_FLOW_BIG_LDS_EPI",      &cv_flow::big_lds_epi,      true,  0,  0,       0, {},               kAnyBuild, true},
+    {"fused_band",      "CV_FLOW_BAND",             &cv_flow::fused_band,       true,  0,  0,       0, {},               kAnyBuild, true},
+    {"band_qkv",        "CV_FLOW_BAND_QKV",         &cv_flow::band_qkv,         true,  0,  0,       0, {},               kAnyBuild, true},
+    {"ln_qkv",          "CV_FLOW_LN_QKV",           &cv_flow::ln_qkv,           true,  0,  0,       0, {},               kAnyBuild, true},
+    {"band_bm",         "CV_FLOW_BAND_BM",          &cv_flow::band_bm,          false, 0,  0,       4, {0, 32, 48, 64},  kAnyBuild, true},
+    {"band_pipe",       "CV_FLOW_BAND_PIPE",        &cv_flow::band_pipe,        false, 0,  2,       0, {},               kAnyBuild, true},
+    {"band_stagger",    "CV_FLOW_BAND_STAGGER",     &cv_flow::band_stagger,     false, 0,  64,      0, {},               0,         true},
+    {"fused_tail",      "CV_FLOW_TAIL",             &cv_flow::fused_tail,       true,  0,  0,       0, {},               0,         true},
+    {"tail_ring",       "CV_FLOW_TAIL_RING",        &cv_flow::tail_ring,        false, INT_MIN, INT_MAX, 0, {},          kAnyBuild, true},      // anything: 16 stays, every other value becomes 8
+    {"est_streams",     nullptr,                    &cv_flow::est_streams,      false, 1,  2,       0, {},               kAnyBuild, true},
+    {"eager_streams",   "CV_FLOW_EAGER_STREAMS",    &cv_flow::eager_streams,    false, 1,  2,       0, {},               1,         false},     // read per solve, by eager passes only
+    {"enc_batch",       "CV_FLOW_ENC_BATCH",        &cv_flow::enc_batch,        true,  0,  0,       0, {},               kAnyBuild, false},     // the encoder is never captured
+    {"graph_max_rows",  "CV_FLOW_GRAPH_MAX_ROWS",   &cv_flow::graph_max_rows,   false, 0,  INT_MAX, 0, {},               kAnyBuild, true},
 };
 
 // Graph capture is illegal on the legacy default stream: NULL maps to a handle-owned blocking stream (implicitly ordered with it).
@@ -287,51 +316,28 @@ static void flow_finalize(cv_flow* m) {
             m->ust.push_back(u);
         }
     }
-    if (const char* e = getenv("CV_FLOW_NTILE")) m->flow_ntile = atoi(e);
-    // dev knobs of the large-M kernel set for A/B runs through bench.py (options of the same names without the prefix)
-    if (const char* e = getenv("CV_FLOW_GRAPH_MAX_ROWS")) m->graph_max_rows = atoi(e);
-    if (const char* e = getenv("CV_FLOW_BIG_ROWS")) m->big_rows = atoi(e);
-    if (const char* e = getenv("CV_FLOW_BIG_PERSIST")) m->big_persist = atoi(e);
-    if (const char* e = getenv("CV_FLOW_BIG_TILE0")) m->big_tile0 = atoi(e);
-    if (const char* e = getenv("CV_FLOW_BIG_TILE1")) m->big_tile1 = atoi(e);
-    if (const char* e = getenv("CV_FLOW_BIG_GLDS")) m->big_glds = atoi(e) != 0;
-    if (const char* e = getenv("CV_FLOW_BIG_LDS_EPI")) m->big_lds_epi = atoi(e) != 0;
-    if (const char* e = getenv("CV_FLOW_ENC_BATCH")) m->enc_batch = atoi(e) != 0;
-    if (const char* e = getenv("CV_FLOW_ATTN2_ROWS")) m->attn2_rows = atoi(e);
-    if (kExperiments) {                                                              // A/B knobs of experiment builds
-        if (const char* e = getenv("CV_FLOW_ATTN32")) m->attn32 = e[0] != '0';
-        if (const char* e = getenv("CV_FLOW_EAGER_STREAMS")) m->eager_streams = atoi(e) >= 2 ? 2 : 1;
-        if (const char* e = getenv("CV_FLOW_TAIL")) m->fused_tail = e[0] != '0';
-        if (const char* e = getenv("CV_FLOW_BAND_STAGGER")) m->band_stagger = atoi(e) > 0 ? atoi(e) : 0;
-    }
-    if (const char* e = getenv("CV_FLOW_RES_TILE")) m->res_tile = atoi(e) == 1;
-    if (const char* e = getenv("CV_FLOW_ATTN32_WAVES")) { const int v = atoi(e); if (v == 0 || v == 2 || v == 4) m->attn32_waves = v; }
-    if (const char* e = getenv("CV_FLOW_BAND_QKV")) m->band_qkv = e[0] != '0';
-    if (const char* e = getenv("CV_FLOW_LN_QKV")) m->ln_qkv = e[0] != '0';
-    if (const char* e = getenv("CV_FLOW_BAND_BM")) m->band_bm = atoi(e);
-    if (const char* e = getenv("CV_FLOW_BAND_PIPE")) m->band_pipe = atoi(e);
-    if (const char* e = getenv("CV_FLOW_BAND")) m->fused_band = e[0] != '0';        // dev knob for A/B runs (also: option "fused_band")
-    if (const char* e = getenv("CV_FLOW_TAIL_RING")) m->tail_ring = atoi(e) == 16 ? 16 : 8;
+    option_apply_env(m, kFlowOptions, "flow option");      // dev knobs for A/B runs through bench.py: the environment variables of the table, checked like the options
+    m->tail_ring = m->tail_ring == 16 ? 16 : 8;            // ("tail_ring" takes anything: 16 stays, every other value is 8)
     if (!unet1) { m->down_conv = get_lin(m, "est.down_conv", C, C, 3, true); m->up_conv = get_lin(m, "est.up_conv", C, C, 3, true); }
     m->final_conv = get_lin(m, "est.final.conv", C, C, 3, true); m->final_ln = get_ln(m, "est.final.ln", C);
     m->final_proj = get_lin(m, "est.final_proj", c.mel, C, 1, true);
     m->finalized = true;
 }
 
-// precision of the Linear / Conv1d products issued by the current entry point (set from the handle's option for the duration of a call)
-static thread_local int tl_bf16_mfma = 0;
-static thread_local int tl_flow_tile = 0, tl_attn_waves = 4, tl_attn_kt = 2, tl_attn_ks = 1, tl_flow_ntile = 0, tl_attn32 = 1, tl_attn32_waves = 0, tl_res_tile = 1;     // tuning knobs of the fused pipeline, per call like the precision
-static thread_local long long* tl_attn_dbg = nullptr; static thread_local long long* tl_gemm_dbg = nullptr; static thread_local int tl_gemm_dbg_which = 0;
-static thread_local int tl_big_tile0 = 0, tl_big_tile1 = 0, tl_big_persist = -1, tl_big_grid_cap = 0, tl_big_glds = 0, tl_big_lds_epi = 1;
-struct PrecisionScope {
-    int prev, pt, pw, pk, ps, pn, p32, p32w, prt, pb0, pb1, pbp, pbc, pbg, pbe;
-    explicit PrecisionScope(const cv_flow* m) : prev(tl_bf16_mfma), pt(tl_flow_tile), pw(tl_attn_waves), pk(tl_attn_kt), ps(tl_attn_ks), pn(tl_flow_ntile), p32(tl_attn32), p32w(tl_attn32_waves), prt(tl_res_tile), pb0(tl_big_tile0), pb1(tl_big_tile1), pbp(tl_big_persist), pbc(tl_big_grid_cap), pbg(tl_big_glds), pbe(tl_big_lds_epi) {
-        tl_bf16_mfma = m->bf16_mfma; tl_flow_tile = m->flow_tile; tl_attn_waves = m->attn_waves; tl_attn_kt = m->attn_kt; tl_attn_ks = m->attn_ks; tl_flow_ntile = m->flow_ntile; tl_attn32 = m->attn32; tl_attn32_waves = m->attn32_waves; tl_res_tile = m->res_tile;
-        tl_big_tile0 = m->big_tile0; tl_big_tile1 = m->big_tile1; tl_big_persist = m->big_persist; tl_big_grid_cap = m->big_grid_cap; tl_big_glds = m->big_glds; tl_big_lds_epi = m->big_lds_epi; tl_attn_dbg = m->attn_dbg_on ? const_cast<cv_flow*>(m)->attn_dbg.as<long long>() : nullptr;
-        tl_gemm_dbg = m->gemm_dbg_on ? const_cast<cv_flow*>(m)->gemm_dbg.as<long long>() : nullptr; tl_gemm_dbg_which = m->gemm_dbg_on;
-    }
-    ~PrecisionScope() { tl_bf16_mfma = prev; tl_flow_tile = pt; tl_attn_waves = pw; tl_attn_kt = pk; tl_attn_ks = ps; tl_flow_ntile = pn; tl_attn32 = p32; tl_attn32_waves = p32w; tl_res_tile = prt; tl_big_tile0 = pb0; tl_big_tile1 = pb1; tl_big_persist = pbp; tl_big_grid_cap = pbc; tl_big_glds = pbg; tl_big_lds_epi = pbe; tl_attn_dbg = nullptr; tl_gemm_dbg = nullptr; tl_gemm_dbg_which = 0; }
+// The handle whose options are in force on this thread: set by every entry point for the duration of the call (FlowScope), read by the launchers that are not
+// handed the handle (conv_cl, the GEMM and attention launchers).  One pointer, so the launchers see the handle's own members - the precision, the tile and
+// attention knobs, the debug buffers - and there is no second set of defaults: a launcher reached outside a scope fails.  Scopes nest (an entry point that
+// calls another restores the outer handle on exit).
+static thread_local const cv_flow* tl_flow = nullptr;
+struct FlowScope {
+    const cv_flow* prev;
+    explicit FlowScope(const cv_flow* m) : prev(tl_flow) { tl_flow = m; }
+    ~FlowScope() { tl_flow = prev; }
 };
+static const cv_flow& flow_opt() {
+    CV_CHECK(tl_flow, "flow: a launcher ran outside a FlowScope (no handle's options are in force on this thread)");
+    return *tl_flow;
+}
 
 // ---- generic conv/linear on channel-last activations -----------------------------------------------------------------
 // rows: M per batch, `a_rows` valid input rows per batch (zero padding outside), tap j reads row (m + j*dil - pad_left)
@@ -345,7 +351,7 @@ static void conv_cl(const Lin& l, const float* A, int a_rows, int M, int batch, 
     a.C = C; a.c_batch = (long long)M * ldc; a.c_len = (long long)M * ldc; a.ldc = ldc; a.c_off = 0; a.M = M; a.N = l.N;
     a.act = act; a.act_p = act_p; a.res = res; a.res_batch = (long long)M * ldc; a.out_scale = 1.f;
     a.row_scale = row_scale; a.row_scale_batch = M; a.accumulate = 0;
-    a.a_bf16 = tl_bf16_mfma && l.bf16;
+    a.a_bf16 = flow_opt().bf16_mfma && l.bf16;
     gemm_conv(a, l.bf16, batch, s);
 }
 static void lin_cl(const Lin& l, const float* A, long long rows, float* C, int act, const float* res, hipStream_t s, int pro = ACT_NONE) {
@@ -401,7 +407,7 @@ static void conformer_layer(cv_flow* m, const ConformerW& w, float* x, int T, co
         at.B = 1; at.H = H; at.kv_group = 1; at.Tq = T; at.Tk = T; at.scale = 0.125f;
         at.mask_mode = chunk > 0 ? MASK_CHUNK : MASK_NONE; at.chunk = chunk;
         at.rel_bd = bd; at.bd_batch = 0; at.bd_head = (long long)T * P; at.bd_row = P;
-        at.bf16 = tl_bf16_mfma;
+        at.bf16 = m->bf16_mfma;
         attention(at, s);
     }
     lin_cl(w.out, att, R, x, ACT_NONE, x, s);
@@ -524,7 +530,8 @@ static void ln_gemm_bf16(const Lin& l, const LN* ln, float eps, const float* x, 
     // 32x64 9.9 us, 64x64 13.9 us, 64x128 ~16 us, 64x192 22.6 us.  A workgroup of this kernel is one dependent chain (load burst -> LayerNorm ->
     // MFMAs -> epilogue) and a CU ingests only a few tens of bytes per cycle, so what helps is MANY small co-resident workgroups whose
     // chains overlap, not fewer re-reads; the big tiles stay selectable for other shapes / later pipelined variants.
-    int tile = tl_flow_tile;
+    const cv_flow& o = flow_opt();
+    int tile = o.flow_tile;
     if (tile == 0) tile = 3;
     auto grid = [&](int bm, int bn) { return dim3((unsigned)(((M + bm - 1) / bm) * ((l.N + bn - 1) / bn))); };
     if (tile == 1) hipLaunchKernelGGL((flow_gemm_kernel<64, 64, 1, 0>), grid(64, 64), dim3(256), 0, s, a);
@@ -533,7 +540,7 @@ static void ln_gemm_bf16(const Lin& l, const LN* ln, float eps, const float* x, 
         // two N tiles per workgroup when the single-tile grid would not fit the 768 resident workgroups (3 per CU) in one round but half of it does
         // (QKV at T = 674: 1032 -> 516 workgroups; FF1 has 688 and stays single-tile): the LayerNorm prologue is paid once per pair
         const unsigned g1 = grid(32, 64).x;
-        if (tl_flow_ntile != 1 && (tl_flow_ntile == 2 || (g1 > 768 && g1 <= 1536)) && l.N % 128 == 0)
+        if (o.flow_ntile != 1 && (o.flow_ntile == 2 || (g1 > 768 && g1 <= 1536)) && l.N % 128 == 0)
             hipLaunchKernelGGL((flow_gemm_kernel<32, 64, 1, 0, 2>), grid(32, 128), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((flow_gemm_kernel<32, 64, 1, 0>), grid(32, 64), dim3(256), 0, s, a);
     }
@@ -546,7 +553,7 @@ static void gemm_bf16_res(const Lin& l, const bf16_t* A, int lda, int M, float* 
     a.A = A; a.lda = lda; a.W = reinterpret_cast<const bf16_t*>(l.w); a.Kp = l.Kp; a.bias = l.b; a.M = M; a.N = l.N; a.K = l.K;
     a.C = C; a.ldc = l.N; a.res = res; a.n_row = l.N;
     // 32 x 64 tiles; 32 x 32 (option "res_tile" = 1; the same k order per element: the same bits) doubles the workgroups of these N = 256 GEMMs (172 at M = 1348)
-    if (tl_res_tile == 1 && l.N % 32 == 0) { hipLaunchKernelGGL((flow_gemm_kernel<32, 32, 0, 1>), dim3(((M + 31) / 32) * ((l.N + 31) / 32)), dim3(256), 0, s, a); return; }
+    if (flow_opt().res_tile == 1 && l.N % 32 == 0) { hipLaunchKernelGGL((flow_gemm_kernel<32, 32, 0, 1>), dim3(((M + 31) / 32) * ((l.N + 31) / 32)), dim3(256), 0, s, a); return; }
     const unsigned g = ((M + 31) / 32) * ((l.N + 63) / 64);
     hipLaunchKernelGGL((flow_gemm_kernel<32, 64, 0, 1>), dim3(g), dim3(256), 0, s, a);
 }
@@ -559,11 +566,12 @@ static void ln_bf16(const LN& ln, float eps, const float* x, int M, int K, bf16_
 // persistent grid (flow_big.h): at most the workgroups that are resident at once - a workgroup then walks its run of tiles with the stage pipeline running across them
 static unsigned big_grid(int M, int N, int bm, int bn) {
     const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-    if (tl_big_persist < 0) return (unsigned)tiles;            // option big_persist = -1: one tile per workgroup (the first form, kept for A/B runs)
+    const cv_flow& o = flow_opt();
+    if (o.big_persist < 0) return (unsigned)tiles;            // option big_persist = -1: one tile per workgroup (the first form, kept for A/B runs)
     const int lds = 2 * (bm + bn) * 32 * 4;
-    const int per_cu = tl_big_persist > 0 ? tl_big_persist : std::max(1, std::min(160 * 1024 / lds, 4));       // 0: LDS-limited residency, at most 4 (16 waves) per CU
+    const int per_cu = o.big_persist > 0 ? o.big_persist : std::max(1, std::min(160 * 1024 / lds, 4));       // 0: LDS-limited residency, at most 4 (16 waves) per CU
     const long long g = std::min<long long>(tiles, (long long)per_cu * 256);
-    return (unsigned)(tl_big_grid_cap > 0 ? std::min<long long>(g, tl_big_grid_cap) : g);     // test hook: a handful of workgroups walk many tiles each
+    return (unsigned)(o.big_grid_cap > 0 ? std::min<long long>(g, o.big_grid_cap) : g);     // test hook: a handful of workgroups walk many tiles each
 }
 template <int OMODE, bool GLDS>
 static void gemm_big_launch2(const FlowGemmArgs& a, int tile, hipStream_t s) {
@@ -574,7 +582,7 @@ static void gemm_big_launch2(const FlowGemmArgs& a, int tile, hipStream_t s) {
 }
 template <int OMODE>
 static void gemm_big_launch(const FlowGemmArgs& a, int tile, hipStream_t s) {
-    if (tl_big_glds) gemm_big_launch2<OMODE, true>(a, tile, s); else gemm_big_launch2<OMODE, false>(a, tile, s);
+    if (flow_opt().big_glds) gemm_big_launch2<OMODE, true>(a, tile, s); else gemm_big_launch2<OMODE, false>(a, tile, s);
 }
 // out = act(A W^T + b) as bf16 (columns >= n_row to the transposed, key-permuted V^T), A = bf16 rows (LayerNorm already applied)
 static void gemm_big_bf16(const Lin& l, const bf16_t* A, int M, int act, bf16_t* out, int ldo, int n_row, bf16_t* outT, long long t_batch, int ldt, int rows_per_batch,
@@ -583,18 +591,20 @@ static void gemm_big_bf16(const Lin& l, const bf16_t* A, int M, int act, bf16_t*
     FlowGemmArgs a{};
     a.A = A; a.lda = l.K; a.W = reinterpret_cast<const bf16_t*>(l.w); a.Kp = l.Kp; a.bias = l.b; a.M = M; a.N = l.N; a.K = l.K; a.act = act;
     a.out = out; a.ldo = ldo; a.n_row = n_row; a.outT = outT; a.t_batch = t_batch; a.ldt = ldt; a.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : M;
-    a.lds_epilogue = tl_big_lds_epi;
-    if (tl_gemm_dbg && tl_gemm_dbg_which == (outT ? 1 : 2)) a.dbg = tl_gemm_dbg;
-    gemm_big_launch<0>(a, tl_big_tile0 ? tl_big_tile0 : 3, s);
+    const cv_flow& o = flow_opt();
+    a.lds_epilogue = o.big_lds_epi;
+    if (o.gemm_dbg_on == (outT ? 1 : 2)) a.dbg = o.gemm_dbg.as<long long>();
+    gemm_big_launch<0>(a, o.big_tile0 ? o.big_tile0 : 3, s);
 }
 // C = A_bf16 W^T + b (+ res), fp32
 static void gemm_big_res(const Lin& l, const bf16_t* A, int lda, int M, float* C, const float* res, hipStream_t s) {
     CV_CHECK(l.bf16 && l.K % 32 == 0 && l.taps == 1 && l.N % 4 == 0 && lda % 8 == 0, "gemm_big_res: needs bf16 weights, K % 32 == 0");
     FlowGemmArgs a{};
     a.A = A; a.lda = lda; a.W = reinterpret_cast<const bf16_t*>(l.w); a.Kp = l.Kp; a.bias = l.b; a.M = M; a.N = l.N; a.K = l.K;
-    a.C = C; a.ldc = l.N; a.res = res; a.n_row = l.N; a.lds_epilogue = tl_big_lds_epi;
-    if (tl_gemm_dbg && tl_gemm_dbg_which == (l.K <= 512 ? 3 : 4)) a.dbg = tl_gemm_dbg;
-    gemm_big_launch<1>(a, tl_big_tile1 ? tl_big_tile1 : 3, s);
+    const cv_flow& o = flow_opt();
+    a.C = C; a.ldc = l.N; a.res = res; a.n_row = l.N; a.lds_epilogue = o.big_lds_epi;
+    if (o.gemm_dbg_on == (l.K <= 512 ? 3 : 4)) a.dbg = o.gemm_dbg.as<long long>();
+    gemm_big_launch<1>(a, o.big_tile1 ? o.big_tile1 : 3, s);
 }
 // causal Conv1d / Linear over bf16 rows of nz requests of T rows each (ResNet blocks of a large pass): C = conv(A) + b (+ res), fp32
 template <bool GLDS>
@@ -606,11 +616,12 @@ static void conv_big_launch(const FlowGemmArgs& a, int tile, hipStream_t s) {
 }
 static void conv_big(const Lin& l, const bf16_t* A, int T, int nz, int pad_left, float* C, const float* res, const void* zeros, hipStream_t s) {
     CV_CHECK(l.bf16 && l.K % 64 == 0 && l.N % 4 == 0 && l.Kp == l.K, "conv_big: needs bf16 weights and K % 64 == 0");
+    const cv_flow& o = flow_opt();
     FlowGemmArgs a{};
     a.A = A; a.lda = l.K; a.W = reinterpret_cast<const bf16_t*>(l.w); a.Kp = l.Kp; a.bias = l.b; a.M = nz * T; a.N = l.N; a.K = l.K;
-    a.C = C; a.ldc = l.N; a.res = res; a.n_row = l.N; a.taps = l.taps; a.pad_left = pad_left; a.rows_per_batch = T; a.zeros = zeros; a.lds_epilogue = tl_big_lds_epi;
-    const int tile = tl_big_tile1 ? tl_big_tile1 : 3;
-    if (tl_big_glds) conv_big_launch<true>(a, tile, s); else conv_big_launch<false>(a, tile, s);
+    a.C = C; a.ldc = l.N; a.res = res; a.n_row = l.N; a.taps = l.taps; a.pad_left = pad_left; a.rows_per_batch = T; a.zeros = zeros; a.lds_epilogue = o.big_lds_epi;
+    const int tile = o.big_tile1 ? o.big_tile1 : 3;
+    if (o.big_glds) conv_big_launch<true>(a, tile, s); else conv_big_launch<false>(a, tile, s);
 }
 // everything between the attention of block `t` and the QKV GEMM of the next block - or, with `q`, up to and including that GEMM - in one launch, 64 / 48 / 32 rows
 // per workgroup (flow_band.h)
@@ -699,29 +710,30 @@ static void attn_flow32_launch(const AttnFlowArgs& a, int waves, hipStream_t s) 
 }
 static void attn_flow(const bf16_t* qk, int ld, int inner, const bf16_t* vt, long long vt_batch, int ldt, bf16_t* o, int B, int H, int T, int chunk, hipStream_t s, const int* klen = nullptr,
                       bool big = false) {
+    const cv_flow& opt = flow_opt();
     AttnFlowArgs a{};
-    a.klen = klen; a.dbg = tl_attn_dbg;
+    a.klen = klen; a.dbg = opt.attn_dbg_on ? opt.attn_dbg.as<long long>() : nullptr;
     a.q = qk; a.k = qk + inner; a.ld = ld; a.vt = vt; a.vt_batch = vt_batch; a.ldt = ldt; a.o = o; a.ldo = inner;
     a.B = B; a.H = H; a.T = T; a.scale = 0.125f; a.mask_mode = chunk > 0 ? MASK_CHUNK : MASK_NONE; a.chunk = chunk;
     const dim3 g2((unsigned)(((T + 31) / 32) * H * B)), g4((unsigned)(((T + 63) / 64) * H * B));
-    if (tl_attn32) {
+    if (opt.attn32) {
         // 128 queries per workgroup (4 waves).  64 (2 waves; option "attn32_waves" = 2) fill more CUs for a single utterance (176 instead of 96 workgroups at T = 674) and
         // measured SLOWER: 39.2 vs 37.5 ms per flow.inference (tools/probe_flow_r6b.py) - each K / V tile then serves half the queries.  Same bits either way.
-        attn_flow32_launch(a, tl_attn32_waves == 2 ? 2 : 4, s);
+        attn_flow32_launch(a, opt.attn32_waves == 2 ? 2 : 4, s);
         return;
     }
 #ifdef CV_BUILD_EXPERIMENTS      // attn_flow_kernel (flow_fused.h), the attention of rounds 2-5 in its workgroup shapes: superseded by attn_flow32_kernel, kept for A/B builds (option attn32 = 0)
     // 128-query workgroups (QG = 2): the same arithmetic per query as attn_flow_kernel<4, 2, 2>, so only that default may be replaced
-    if (big && tl_attn_ks == 2) { hipLaunchKernelGGL((attn_flow_kernel<4, 2, 2, 2>), dim3((unsigned)(((T + 127) / 128) * H * B)), dim3(512), 0, s, a); return; }
-    if (tl_attn_ks == 2) { hipLaunchKernelGGL((attn_flow_kernel<4, 2, 2>), g4, dim3(512), 0, s, a); return; }
+    if (big && opt.attn_ks == 2) { hipLaunchKernelGGL((attn_flow_kernel<4, 2, 2, 2>), dim3((unsigned)(((T + 127) / 128) * H * B)), dim3(512), 0, s, a); return; }
+    if (opt.attn_ks == 2) { hipLaunchKernelGGL((attn_flow_kernel<4, 2, 2>), g4, dim3(512), 0, s, a); return; }
     // 3 / 4 key splits: 12 / 16 waves on the same 64 queries, 192 / 256 keys per iteration - 4 / 3 iterations instead of 6 at T = 674 (round 3 probe)
-    if (tl_attn_ks == 3) { hipLaunchKernelGGL((attn_flow_kernel<4, 3, 3>), g4, dim3(768), 0, s, a); return; }
-    if (tl_attn_ks == 4) { hipLaunchKernelGGL((attn_flow_kernel<4, 4, 4>), g4, dim3(1024), 0, s, a); return; }
-    if (tl_attn_waves == 2) {
-        if (tl_attn_kt == 2) hipLaunchKernelGGL((attn_flow_kernel<2, 2>), g2, dim3(128), 0, s, a);
+    if (opt.attn_ks == 3) { hipLaunchKernelGGL((attn_flow_kernel<4, 3, 3>), g4, dim3(768), 0, s, a); return; }
+    if (opt.attn_ks == 4) { hipLaunchKernelGGL((attn_flow_kernel<4, 4, 4>), g4, dim3(1024), 0, s, a); return; }
+    if (opt.attn_waves == 2) {
+        if (opt.attn_kt == 2) hipLaunchKernelGGL((attn_flow_kernel<2, 2>), g2, dim3(128), 0, s, a);
         else hipLaunchKernelGGL((attn_flow_kernel<2, 1>), g2, dim3(128), 0, s, a);
     } else {
-        if (tl_attn_kt == 2) hipLaunchKernelGGL((attn_flow_kernel<4, 2>), g4, dim3(256), 0, s, a);
+        if (opt.attn_kt == 2) hipLaunchKernelGGL((attn_flow_kernel<4, 2>), g4, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((attn_flow_kernel<4, 1>), g4, dim3(256), 0, s, a);
     }
 #else
@@ -800,7 +812,7 @@ static void stage_blocks(cv_flow* m, const StageW& st, float* x, int T, int nz, 
         at.o = att; at.o_batch = (long long)T * inner; at.o_row = inner; at.o_head = 64;
         at.B = nz; at.H = H; at.kv_group = 1; at.Tq = T; at.Tk = T; at.scale = 0.125f;
         at.mask_mode = chunk > 0 ? MASK_CHUNK : MASK_NONE; at.chunk = chunk; at.rel_bd = nullptr;
-        at.bf16 = tl_bf16_mfma; at.klen = klen;
+        at.bf16 = m->bf16_mfma; at.klen = klen;
         attention(at, s);
         lin_cl(t.out, att, R, x, ACT_NONE, x, s);
         ln_rows(t.norm3, x, n, R, C, 1e-5f, s);
@@ -826,7 +838,7 @@ static void estimator_forward(cv_flow* m, int T, int t_row, int t_rows_total, bo
         const long long rpb = t_shared ? R : T;          // rows per time-embedding row
         float* x = pp[flip];                             // stage output (cur never aliases it)
         // CausalResnetBlock1D (decoder.py:65-85 + matcha ResnetBlock1D): block1 -> + mlp(t) -> block2 -> + res_conv(x)
-        const bool fused = tl_bf16_mfma && m->fused && C <= 256 && m->wbf16;
+        const bool fused = m->bf16_mfma && m->fused && C <= 256 && m->wbf16;
         const int din = st.res.conv1.K;
         if (fused && m->big_rows > 0 && R >= m->big_rows && din % 64 == 0 && C % 64 == 0) {
             // large pass (flow_big.h): the block's input and Mish(LN(block1)) are rounded to bf16 ONCE (the small bf16 tiles round them per tap and per N tile
@@ -879,7 +891,7 @@ static void unet1_forward(cv_flow* m, int T, int t_row, int t_rows_total, bool t
     const auto& c = m->cfg; const int C = c.est_ch, G = 8;
     float* pp[2] = {m->s_a.as<float>(), m->s_c.as<float>()};
     float* xb = m->s_b.as<float>(); float* cat = m->s_cat.as<float>(); double* gn = m->u_gn.as<double>();
-    const bool fused = tl_bf16_mfma && m->fused && C <= 256 && m->wbf16;
+    const bool fused = m->bf16_mfma && m->fused && C <= 256 && m->wbf16;
     auto conv = [&](const Lin& l, const float* in, int Tn, float* out, const float* res) { conv_cl(l, in, Tn, Tn, nz, l.taps / 2, 1, out, ACT_NONE, 0.f, res, s); };
     const float* cur = m->s_in.as<float>();
     int Tc = T, flip = 0, level = 0;
@@ -911,7 +923,7 @@ static void unet1_forward(cv_flow* m, int T, int t_row, int t_rows_total, bool t
         else {
             GemmConvArgs a{};
             a.A = x; a.a_batch = (long long)Tc * C; a.a_len = (long long)Tc * C; a.K = l.K; a.taps = l.taps; a.pro = ACT_NONE; a.W = l.w; a.Kp = l.Kp; a.bias = l.b;
-            a.C = y; a.N = l.N; a.act = ACT_NONE; a.out_scale = 1.f; a.a_bf16 = tl_bf16_mfma && l.bf16;
+            a.C = y; a.N = l.N; a.act = ACT_NONE; a.out_scale = 1.f; a.a_bf16 = m->bf16_mfma && l.bf16;
             int Tn;
             if (u.post == 2) {               // Downsample1D: output row j = rows 2 j - 1 .. 2 j + 1, contiguous in a channel-last sequence
                 Tn = (Tc - 1) / 2 + 1;
@@ -1010,7 +1022,7 @@ static void dit_group_conv(const Lin& l, const float* A, float* C, const float* 
     a.pro = ACT_NONE; a.W = l.w; a.Kp = l.Kp; a.ldw = 0; a.w_batch = (long long)gc * l.taps * l.Kp; a.bias = l.b; a.bias_batch = gc;
     a.C = C; a.c_batch = gc; a.c_len = (long long)(T - 1) * D + gc; a.ldc = D; a.c_off = 0; a.M = T; a.N = gc;
     a.act = ACT_MISH; a.res = res; a.res_batch = gc; a.out_scale = 1.f; a.row_scale = nullptr; a.accumulate = 0;
-    a.a_bf16 = tl_bf16_mfma && l.bf16;
+    a.a_bf16 = flow_opt().bf16_mfma && l.bf16;
     gemm_conv(a, l.bf16, G, s);
 }
 // Linear with the adaLN-zero gate:  C = res + gate[m / rows_per_gate] * (A W^T + b)
@@ -1022,7 +1034,7 @@ static void lin_gated(const Lin& l, const float* A, long long rows, float* C, co
     a.C = C; a.c_batch = 0; a.c_len = rows * l.N; a.ldc = l.N; a.c_off = 0; a.M = (int)rows; a.N = l.N;
     a.act = ACT_NONE; a.res = res; a.res_batch = 0; a.out_scale = 1.f; a.row_scale = nullptr; a.accumulate = 0;
     a.col_scale = gate; a.col_scale_rows = (int)rows_per_gate; a.col_scale_stride = gate_stride;
-    a.a_bf16 = tl_bf16_mfma && l.bf16;
+    a.a_bf16 = flow_opt().bf16_mfma && l.bf16;
     gemm_conv(a, l.bf16, 1, s);
 }
 // s_in packed [nz][T][4 mel] as [x | mu | spks | cond] (the in_proj columns are permuted to this order by the repacker) -> s_out [nz][T][mel];
@@ -1054,7 +1066,7 @@ static void dit_forward(cv_flow* m, int T, int t_row, int t_rows_total, bool t_s
         at.v = qkv + 2 * D; at.v_batch = at.q_batch; at.v_row = 3 * D; at.v_head = 64;
         at.o = att; at.o_batch = (long long)T * D; at.o_row = D; at.o_head = 64;
         at.B = nz; at.H = H; at.kv_group = 1; at.Tq = T; at.Tk = T; at.scale = 0.125f;
-        at.mask_mode = chunk > 0 ? MASK_CHUNK : MASK_NONE; at.chunk = chunk; at.rel_bd = nullptr; at.bf16 = tl_bf16_mfma; at.klen = m->cur_klen;
+        at.mask_mode = chunk > 0 ? MASK_CHUNK : MASK_NONE; at.chunk = chunk; at.rel_bd = nullptr; at.bf16 = m->bf16_mfma; at.klen = m->cur_klen;
         attention(at, s);
         lin_gated(w.out, att, R, other, cur, mod + 2 * D, rpb, gbs, s);              // x + gate_msa * to_out(attn)
         std::swap(cur, other);
@@ -1159,40 +1171,14 @@ int cv_flow_finalize(cv_flow* m) { return guarded([&] { CV_CHECK(m, "null handle
 int cv_flow_set_option(cv_flow* m, const char* name, int32_t value) {
     return guarded([&] {
         CV_CHECK(m && name, "null argument");
-        if (std::string(name) == "use_graph") { m->use_graph = value != 0; drop_graphs(m); }
-        else if (std::string(name) == "bf16_mfma") { m->bf16_mfma = value != 0; drop_graphs(m); }      // captured graphs bake the kernel choice
-        else if (std::string(name) == "flow_tile") { CV_CHECK(value >= 0 && value <= 4, "flow_tile must be 0..4"); m->flow_tile = value; drop_graphs(m); }
-        else if (std::string(name) == "attn32") { need_experiments(value == 0, "flow option attn32 = 0"); m->attn32 = value != 0; drop_graphs(m); }
-        else if (std::string(name) == "res_tile") { CV_CHECK(value == 0 || value == 1, "res_tile must be 0 or 1"); m->res_tile = value; drop_graphs(m); }
-        else if (std::string(name) == "attn32_waves") { CV_CHECK(value == 0 || value == 2 || value == 4, "attn32_waves must be 0, 2 or 4"); m->attn32_waves = value; drop_graphs(m); }
-        else if (std::string(name) == "attn_ks") { CV_CHECK(value >= 1 && value <= 4, "attn_ks must be 1 .. 4"); m->attn_ks = value; drop_graphs(m); }
-        else if (std::string(name) == "attn_kt") { CV_CHECK(value == 1 || value == 2, "attn_kt must be 1 or 2"); m->attn_kt = value; drop_graphs(m); }
-        else if (std::string(name) == "attn_waves") { CV_CHECK(value == 2 || value == 4, "attn_waves must be 2 or 4"); m->attn_waves = value; drop_graphs(m); }
-        else if (std::string(name) == "eager_streams") { CV_CHECK(value == 1 || value == 2, "eager_streams must be 1 or 2"); need_experiments(value == 2, "flow option eager_streams = 2"); m->eager_streams = value; }
-        else if (std::string(name) == "est_streams") { CV_CHECK(value == 1 || value == 2, "est_streams must be 1 or 2"); m->est_streams = value; drop_graphs(m); }
-        else if (std::string(name) == "graph_max_rows") { CV_CHECK(value >= 0, "graph_max_rows must be >= 0"); m->graph_max_rows = value; drop_graphs(m); }
-        else if (std::string(name) == "graph_cap") { CV_CHECK(value >= 1 && value <= 256, "graph_cap must be 1 .. 256"); drop_graphs(m); m->graph_cap = (size_t)value; }
-        else if (std::string(name) == "fused_tail") { need_experiments(value != 0, "flow option fused_tail"); m->fused_tail = value != 0; drop_graphs(m); }
-        else if (std::string(name) == "band_qkv") { m->band_qkv = value != 0; drop_graphs(m); }
-        else if (std::string(name) == "ln_qkv") { m->ln_qkv = value != 0; drop_graphs(m); }
-        else if (std::string(name) == "band_stagger") { CV_CHECK(value >= 0 && value <= 64, "band_stagger must be 0 .. 64"); need_experiments(value != 0, "flow option band_stagger"); m->band_stagger = value; drop_graphs(m); }
-        else if (std::string(name) == "band_pipe") { CV_CHECK(value >= 0 && value <= 2, "band_pipe must be 0, 1 or 2"); m->band_pipe = value; drop_graphs(m); }
-        else if (std::string(name) == "band_bm") { CV_CHECK(value == 0 || value == 32 || value == 48 || value == 64, "band_bm must be 0, 32, 48 or 64"); m->band_bm = value; drop_graphs(m); }
-        else if (std::string(name) == "fused_band") { m->fused_band = value != 0; drop_graphs(m); }      // bf16 mode, large passes: one 64-row band launch between attention and the next QKV GEMM (flow_band.h) on / off
-        else if (std::string(name) == "flow_ntile") { CV_CHECK(value >= 0 && value <= 2, "flow_ntile must be 0, 1 or 2"); m->flow_ntile = value; drop_graphs(m); }
-        else if (std::string(name) == "tail_ring") { m->tail_ring = value == 16 ? 16 : 8; drop_graphs(m); }      // bf16 mode: one row-band launch after each attention (flow_tail.h) on / off
-        else if (std::string(name) == "big_rows") { CV_CHECK(value >= 0, "big_rows must be >= 0"); m->big_rows = value; drop_graphs(m); }
-        else if (std::string(name) == "attn2_rows") { CV_CHECK(value >= 0, "attn2_rows must be >= 0"); m->attn2_rows = value; drop_graphs(m); }
-        else if (std::string(name) == "big_tile0") { CV_CHECK(value >= 0 && value <= 4, "big_tile0 must be 0..4"); m->big_tile0 = value; drop_graphs(m); }
-        else if (std::string(name) == "big_persist") { CV_CHECK(value >= -1 && value <= 8, "big_persist must be -1..8"); m->big_persist = value; drop_graphs(m); }
+        if (const FlowOption* o = option_set(m, kFlowOptions, name, value, "flow option")) {
+            m->tail_ring = m->tail_ring == 16 ? 16 : 8;      // (as in flow_finalize: tail_ring takes anything)
+            if (o->drops_graphs) drop_graphs(m);                // captured graphs bake the kernel choice
+        }
+        // what is more than an int: the two stamp buffers (allocated and cleared when switched on) and the graph cache's size
         else if (std::string(name) == "gemm_dbg") { m->gemm_dbg_on = value; if (value) { m->gemm_dbg.ensure((size_t)65536 * 8 * 8); CV_HIP(hipMemset(m->gemm_dbg.p, 0, m->gemm_dbg.bytes)); } drop_graphs(m); }
         else if (std::string(name) == "attn_dbg") { m->attn_dbg_on = value != 0; if (value) { m->attn_dbg.ensure((size_t)65536 * 8 * 8); CV_HIP(hipMemset(m->attn_dbg.p, 0, m->attn_dbg.bytes)); } drop_graphs(m); }
-        else if (std::string(name) == "big_lds_epi") { m->big_lds_epi = value != 0; drop_graphs(m); }
-        else if (std::string(name) == "enc_batch") m->enc_batch = value != 0;
-        else if (std::string(name) == "big_glds") { m->big_glds = value != 0; drop_graphs(m); }
-        else if (std::string(name) == "big_grid_cap") { CV_CHECK(value >= 0, "big_grid_cap must be >= 0"); m->big_grid_cap = value; drop_graphs(m); }
-        else if (std::string(name) == "big_tile1") { CV_CHECK(value >= 0 && value <= 4, "big_tile1 must be 0..4"); m->big_tile1 = value; drop_graphs(m); }
-        else if (std::string(name) == "fused") { m->fused = value != 0; drop_graphs(m); }              // bf16 mode: fused transformer blocks (flow_fused.h) on / off
+        else if (std::string(name) == "graph_cap") { CV_CHECK(value >= 1 && value <= 256, "graph_cap must be 1 .. 256"); drop_graphs(m); m->graph_cap = (size_t)value; }
         else throw Error(std::string("unknown option ") + name);
     });
 }
@@ -1234,14 +1220,14 @@ void cv_flow_destroy(cv_flow* m) {
 int cv_flow_encoder(cv_flow* m, const float* tok_emb, int32_t n_tok, const float* context, int32_t streaming, float* h_out, void* stream) {
     return guarded([&] { CV_CHECK(m && m->finalized && tok_emb && h_out, "cv_flow_encoder: bad arguments");
                          CV_CHECK(m->cfg.estimator == 0, "cv_flow_encoder: CausalMaskedDiffWithDiT has no conformer encoder (its front is PreLookaheadLayer, inside cv_flow_inference)");
-                         PrecisionScope prec(m);
+                         FlowScope scope(m);
                          flow_encoder(m, tok_emb, n_tok, context, streaming, h_out, as_stream(stream)); });
 }
 
 static void flow_estimator_call(cv_flow* m, const float* x, const float* mask, const int32_t* key_len, const float* mu, const float* t, const float* spks,
                                 const float* cond, int32_t T, int32_t streaming, float* out, void* stream) {
     CV_CHECK(m && m->finalized && x && mu && t && spks && cond && out && T > 0, "cv_flow_estimator: bad arguments");
-    PrecisionScope prec(m);
+    FlowScope scope(m);
     hipStream_t s = as_stream(stream);
     const auto& c = m->cfg;
     const bool dit = c.estimator == 1;
@@ -1270,7 +1256,7 @@ static void flow_profile_block(cv_flow* m, int nz, int T, int reps, float* us3, 
     const auto& c = m->cfg; const int C = c.est_ch, H = c.est_heads, inner = H * 64; const long long R = (long long)nz * T;
     CV_CHECK(m->finalized && c.estimator == 0 && m->wbf16 && nz >= 2 && T > 0 && reps > 0 && us3, "cv_flow_profile_block: needs the bf16-mode U-Net estimator");
     CV_CHECK(m->stages.size() >= 2 && m->stages[1].tf.size() >= 2 && m->stages[1].tf[0].band, "cv_flow_profile_block: no band stream for this configuration");
-    PrecisionScope prec(m);
+    FlowScope scope(m);
     est_reserve(m, T, nz);
     const TBlockW& t = m->stages[1].tf[0];
     const long long vt_batch = (long long)inner * m->vt_pitch;
@@ -1332,7 +1318,7 @@ int cv_flow_estimator_masked(cv_flow* m, const float* x, const float* mask, cons
 // embedding [nu][spk_dim], mel_out [nu][mel][T - mel_len1].  nu = 1 is cv_flow_inference.
 static void flow_inference(cv_flow* m, int nu, const int32_t* token_ids, int n_tok, const float* prompt_feat, int mel_len1, const float* embedding,
                            const float* noise_cl, int streaming, int finalize, int n_timesteps, float* mel_out, int32_t* mel_len2_out, void* stream) {
-    PrecisionScope prec(m);
+    FlowScope scope(m);
     const auto& c = m->cfg; const int d = c.dim;
     hipStream_t s = resolve(m, stream);
     void* stream_r = reinterpret_cast<void*>(s);
@@ -1389,7 +1375,7 @@ static void flow_inference(cv_flow* m, int nu, const int32_t* token_ids, int n_t
 // utterance alone.  The valid rows are therefore bit-identical to the single pass; the padded rows compute finite values nobody reads.
 static void flow_inference_ragged(cv_flow* m, int nu, const int32_t* token_ids, const int32_t* n_tok, const float* prompt_feat, const int32_t* mel_len1, const float* embedding,
                                   const float* noise_cl, int streaming, int finalize, int n_timesteps, float* mel_out, int32_t* mel_len2_out, void* stream) {
-    PrecisionScope prec(m);
+    FlowScope scope(m);
     const auto& c = m->cfg; const int d = c.dim;
     hipStream_t s = resolve(m, stream);
     void* stream_r = reinterpret_cast<void*>(s);
@@ -1452,7 +1438,7 @@ static void flow_inference_ragged(cv_flow* m, int nu, const int32_t* token_ids, 
 int cv_flow_solve(cv_flow* m, float* x, const float* mu, const float* spks, const float* cond, int32_t T, int32_t n_timesteps, void* stream) {
     return guarded([&] {
         CV_CHECK(m && m->finalized && x && mu && spks && cond && T > 0 && n_timesteps > 0, "cv_flow_solve: bad arguments");
-        PrecisionScope prec(m);
+        FlowScope scope(m);
         hipStream_t s = resolve(m, stream);
         const auto& c = m->cfg; const size_t per = (size_t)T * c.mel * 4;
         if (T > m->solve_cap || m->f_x.bytes < per || m->f_mu.bytes < per || m->f_cond.bytes < per || m->f_spk.bytes < (size_t)c.mel * 4) {

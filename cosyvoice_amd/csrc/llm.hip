@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include "ops.h"
 #include "tensor_map.h"
+#include "options.h"
 #include "llm_kernels.h"
 #include "llm_batch_kernels.h"
 
@@ -21,14 +22,6 @@ using namespace cv;
 // Options / environment knobs that select a measured no-go (kept as evidence; their kernels are instantiated and their switches accepted only in a library built with
 // -DCV_BUILD_EXPERIMENTS): fused_qkv_attn (qkv_attn_kernel), fused_attn_oproj (attn_oproj_kernel), prefetch (weight-prefetch roles),
 // CV_ATTN_BATCH_GQA (attn_decode_batch_gqa_kernel), CV_DOWN_DEEP (skinny_deep_kernel).
-#ifdef CV_BUILD_EXPERIMENTS
-static constexpr bool kExperiments = true;
-#else
-static constexpr bool kExperiments = false;
-#endif
-static void need_experiments(bool wanted, const char* what) {
-    if (wanted && !kExperiments) throw cv::Error(std::string(what) + " selects an experiment this library was built without (rebuild with CV_BUILD_EXPERIMENTS=1)");
-}
 
 struct cv_llm {
     cv_llm_config cfg{};
@@ -67,7 +60,7 @@ struct cv_llm {
     int pf_rows = 0;
     // decode graph
     hipGraphExec_t graph = nullptr; hipStream_t graph_stream = nullptr; hipStream_t own_stream = nullptr;
-    cv_sampling sp{}; bool sp_valid = false; bool use_graph = true;
+    cv_sampling sp{}; bool sp_valid = false; int use_graph = 1;
     int* host_tokens = nullptr; DecodeState* host_state = nullptr;
     // lock-step batched decode (llm_batch_kernels.h): nb slots, each with its own KV cache / state / token history
     struct Batch {
@@ -104,6 +97,25 @@ struct cv_llm {
         if (host_sp) (void)hipHostFree(host_sp);
     }
 };
+
+// One row per integer option: what cv_llm_set_option accepts by name and llm_finalize from the environment (options.h); the members above say what they do.
+// "drops graphs" here is the captured single-step decode graph.  Not here: batch_attn, batch_packed, batch_fp8 (written out in cv_llm_set_option).
+using LlmOption = Option<cv_llm>;
+static const LlmOption kLlmOptions[] = {
+    // name               environment                  member                       bool   lo       hi       values          product    drops graphs
+    {"use_graph",         nullptr,                     &cv_llm::use_graph,          true,  0,       0,       0, {},          kAnyBuild, true},
+    {"head_rows",         nullptr,                     &cv_llm::head_rows,          false, 1,       2,       0, {},          kAnyBuild, true},
+    {"head_waves",        "CV_HEAD_WAVES",             &cv_llm::head_waves,         false, 0,       0,       2, {4, 7},      kAnyBuild, true},
+    {"attn_splits",       nullptr,                     &cv_llm::attn_splits,        false, 0,       0,       3, {4, 8, 16},  kAnyBuild, true},      // key-range slices per head in the decode attention
+    {"fused_qkv_attn",    "CV_DECODE_FUSED_QKV",       &cv_llm::fused_qkv_attn,     true,  0,       0,       0, {},          0,         true},
+    {"prefetch",          "CV_DECODE_PREFETCH",        &cv_llm::prefetch,           false, 0,       2,       0, {},          0,         true},
+    {"prefetch_shift",    "CV_DECODE_PREFETCH_SHIFT",  &cv_llm::prefetch_shift,     false, INT_MIN, INT_MAX, 0, {},          kAnyBuild, true},
+    {"fused_attn_oproj",  "CV_DECODE_FUSED_O",         &cv_llm::fused_attn_oproj,   false, INT_MIN, INT_MAX, 0, {},          0,         true},      // (stored as given, read as on / off)
+    {"oproj_rblocks",     "CV_OPROJ_RBLOCKS",          &cv_llm::oproj_rblocks,      false, 0,       0,       2, {4, 8},      kAnyBuild, true},
+    {"oproj_waves",       "CV_OPROJ_WAVES",            &cv_llm::oproj_waves,        false, 0,       0,       2, {8, 16},     kAnyBuild, true},
+    {"prefill_rows",      nullptr,                     &cv_llm::prefill_rows,       true,  0,       0,       0, {},          kAnyBuild, false},     // the prefill is never captured
+};
+static void drop_step_graph(cv_llm* m) { if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; } }
 
 static void llm_finalize(cv_llm* m) {
     const auto& c = m->cfg;
@@ -163,14 +175,8 @@ static void llm_finalize(cv_llm* m) {
     m->h.ensure(H * 4); m->qkv.ensure((size_t)m->qkv_dim * 4);
     m->attn_part.ensure((size_t)c.heads * 16 * ATTN_PART * 4);
     m->newtok.ensure((size_t)(c.heads + 2 * c.kv_heads) * 64 * 4);
-    if (kExperiments) if (const char* e = getenv("CV_DECODE_FUSED_QKV")) m->fused_qkv_attn = e[0] != '0';     // dev knob for A/B runs (also: option "fused_qkv_attn")
-    if (const char* e = getenv("CV_HEAD_WAVES")) m->head_waves = atoi(e) == 7 ? 7 : 4;
-    if (kExperiments) if (const char* e = getenv("CV_DECODE_PREFETCH")) m->prefetch = atoi(e);                 // dev knobs for A/B runs (also: options "prefetch", "prefetch_shift")
-    if (const char* e = getenv("CV_DECODE_PREFETCH_SHIFT")) m->prefetch_shift = atoi(e);
+    option_apply_env(m, kLlmOptions, "llm option");        // dev knobs for A/B runs: the environment variables of the table, checked like the options
     m->pf_sink.ensure(64);
-    if (kExperiments) if (const char* e = getenv("CV_DECODE_FUSED_O")) m->fused_attn_oproj = e[0] != '0';      // dev knobs for A/B runs (also: options "fused_attn_oproj", "oproj_rblocks")
-    if (const char* e = getenv("CV_OPROJ_RBLOCKS")) m->oproj_rblocks = atoi(e) == 8 ? 8 : 4;
-    if (const char* e = getenv("CV_OPROJ_WAVES")) m->oproj_waves = atoi(e) == 16 ? 16 : 8;
     m->opart.ensure((size_t)16 * H * 4); m->h2.ensure(H * 4);
     m->act.ensure((size_t)c.inter * 4); m->logits.ensure((size_t)m->V * 4);
     CV_HIP(hipHostMalloc((void**)&m->host_tokens, (size_t)c.max_len * sizeof(int)));
@@ -858,27 +864,7 @@ int cv_llm_set_option(cv_llm* m, const char* name, int32_t value) {
     return guarded([&] {
         CV_CHECK(m && name, "null argument");
         std::lock_guard<std::recursive_mutex> lk(runtime_lock());
-        if (std::string(name) == "use_graph") { m->use_graph = value != 0; if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; } }
-        else if (std::string(name) == "head_rows") { CV_CHECK(value == 1 || value == 2, "head_rows must be 1 or 2"); m->head_rows = value; if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; } }
-        else if (std::string(name) == "fused_attn_oproj" || std::string(name) == "oproj_rblocks" || std::string(name) == "oproj_waves") {
-            CV_CHECK(std::string(name) != "oproj_rblocks" || value == 4 || value == 8, "oproj_rblocks must be 4 or 8");
-            CV_CHECK(std::string(name) != "oproj_waves" || value == 8 || value == 16, "oproj_waves must be 8 or 16");
-            need_experiments(std::string(name) == "fused_attn_oproj" && value != 0, "llm option fused_attn_oproj");
-            (std::string(name) == "fused_attn_oproj" ? m->fused_attn_oproj : std::string(name) == "oproj_rblocks" ? m->oproj_rblocks : m->oproj_waves) = value;
-            if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
-        }
-        else if (std::string(name) == "prefill_rows") m->prefill_rows = value != 0;
-        else if (std::string(name) == "head_waves") { CV_CHECK(value == 4 || value == 7, "head_waves must be 4 or 7"); m->head_waves = value; if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; } }
-        else if (std::string(name) == "fused_qkv_attn") { need_experiments(value != 0, "llm option fused_qkv_attn"); m->fused_qkv_attn = value != 0; if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; } }
-        else if (std::string(name) == "prefetch" || std::string(name) == "prefetch_shift") {
-            CV_CHECK(std::string(name) != "prefetch" || (value >= 0 && value <= 2), "prefetch must be 0, 1 or 2");
-            need_experiments(std::string(name) == "prefetch" && value != 0, "llm option prefetch");
-            (std::string(name) == "prefetch" ? m->prefetch : m->prefetch_shift) = value; if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
-        }
-        else if (std::string(name) == "attn_splits") {       // key-range slices per head in the decode attention (4, 8 or 16)
-            CV_CHECK(value == 4 || value == 8 || value == 16, "attn_splits must be 4, 8 or 16");
-            m->attn_splits = value; if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
-        }
+        if (const LlmOption* o = option_set(m, kLlmOptions, name, value, "llm option")) { if (o->drops_graphs) drop_step_graph(m); }
         else if (std::string(name) == "batch_attn") {
             CV_CHECK(value >= -1 && value <= 2, "batch_attn must be -1 (by slot count and context), 0 (VALU form), 1 (MFMA form) or 2 (MFMA form, one key partition for every slot count)");
             m->batch_attn = value;                               // (every form keeps its own captured step: no graph is dropped)
