@@ -471,6 +471,57 @@ class EspnetEncoder(C1.EspnetEncoder):
         state.len += n_out.value                                 # (rows written past the last emitted token belong to nobody)
         return [int(buf[k]) for k in range(n_out.value)], bool(fin.value)
 
+    # ---- the lock-step batched loop (cv_lm1_batch_*): up to 8 requests share one weight stream per token ------------------------------------------------
+    def batch_begin(self, step, nb):
+        """Size `step` for nb slots, all of them empty."""
+        step.lib.cv_lm1_batch_begin(step.h, C.c_int32(nb), stream_ptr(step.lib))
+        step.slot_bound = [None] * nb
+
+    def batch_bind(self, step, slot, state):
+        """The slot's cache rows and the tables, when either was (re)allocated since the slot was last bound (cv_lm1_batch_bind keeps the slot's position and request)."""
+        self._pos_tables(state.cap)
+        key = (state.ident, self._pos_n)
+        if step.slot_bound[slot] != key:
+            n = self.n_layers
+            rows = (C.c_void_p * n)(*[r.data_ptr() for r in state.rows])
+            tabs = (C.c_void_p * n)(*[t.data_ptr() for t in self._pos_tab])
+            step.lib.cv_lm1_batch_bind(step.h, C.c_int32(slot), rows, tabs, C.c_int32(self._pos_n), C.c_int32(state.cap), stream_ptr(step.lib))
+            step.slot_bound[slot] = key
+
+    def batch_open(self, step, slot, x_row, state, sp, emb_table, uniforms=None, reserve=True):
+        """loop_begin for one slot: the cache is grown ONCE for every position the request can write, bound, and the request parked in the slot.  reserve = False: only
+        the next row is reserved - the caller grows the cache (state.reserve) and rebinds (batch_bind) while the request runs."""
+        t0 = state.len
+        state.reserve(t0 + (int(sp.max_len) if reserve else 0) + 1)
+        self.batch_bind(step, slot, state)
+        u = None if uniforms is None else uniforms.detach().to(torch.float32).cpu().contiguous()
+        step.lib.cv_lm1_batch_open(step.h, C.c_int32(slot), C.c_void_p(x_row.data_ptr()), C.c_int32(t0), C.byref(sp), C.c_void_p(emb_table.data_ptr()), C.c_int32(int(sp.max_len)),
+                                   C.c_void_p(u.data_ptr()) if u is not None else None, C.c_int32(0 if u is None else u.numel()), stream_ptr(step.lib))
+        state.plan = None
+
+    def batch_steps(self, step, states, n):
+        """n lock-step steps; states: {slot: _KVState} of the open slots.  Returns {slot: (tokens emitted by these steps, finished)}."""
+        nb = len(step.slot_bound)
+        for slot, state in states.items():                      # (tables that grew for a request opened since: every open slot moves to the new ones before the step reads them)
+            self.batch_bind(step, slot, state)
+        buf, n_out, fin = (C.c_int32 * (nb * n))(), (C.c_int32 * nb)(), (C.c_int32 * nb)()
+        step.lib.cv_lm1_batch_decode(step.h, C.c_int32(n), buf, n_out, fin, stream_ptr(step.lib))
+        out = {}
+        for slot, state in states.items():
+            state.len += n_out[slot]                             # (rows written past the last emitted token belong to nobody)
+            out[slot] = ([int(buf[slot * n + k]) for k in range(n_out[slot])], bool(fin[slot]))
+        return out
+
+    def batch_release(self, step, slot):
+        step.lib.cv_lm1_batch_release(step.h, C.c_int32(slot))
+        step.slot_bound[slot] = None
+
+    def batch_logits(self, step, slot, n_out):
+        """Test hook: the slot's logits after the last step, on the host."""
+        out = torch.empty(n_out, dtype=F32)
+        step.lib.cv_lm1_batch_logits(step.h, C.c_int32(slot), C.c_void_p(out.data_ptr()), stream_ptr(step.lib))
+        return out
+
     def _forward_rows(self, xs, t1, state, t0):
         x = self._embed(xs, t1)
         for i in range(self.n_layers):
@@ -564,29 +615,114 @@ class TransformerLM(C1.TransformerLM):
         x = self.text_encoder.forward(self.k.gather(self.text_emb, ids))
         return self.k.linear(x, self.affine, x.shape[0])
 
+    def _lm_input(self, text, prompt_text, prompt_speech_token, embedding):
+        """[sos | speaker | encoded text | task id | prompt speech tokens] (llm.py:176-193) on the device -> (rows [L, D], L, text length).  Called under the stage lock."""
+        K, D = self.k, self.llm_input_size
+        ids = torch.cat([prompt_text, text], dim=1).reshape(-1).to(torch.int32)
+        n_text, n_prompt = int(text.shape[1]), int(prompt_speech_token.shape[1])
+        has_spk = embedding.shape[0] != 0
+        L = 1 + int(has_spk) + ids.numel() + 1 + n_prompt
+        lm_input = K.new(L, D)
+        r = 0
+        lm_input[r:r + 1].copy_(self.llm_emb[self.sos:self.sos + 1]); r += 1
+        if has_spk:
+            e = torch.nn.functional.normalize(embedding.float().cpu(), dim=1)     # 192 numbers: normalised on the host
+            K.linear(K.put(e), self.spk_affine, 1, out=lm_input[r:]); r += 1
+        enc = self.encode_text(ids)
+        lm_input[r:r + ids.numel()].copy_(enc); r += ids.numel()
+        lm_input[r:r + 1].copy_(self.llm_emb[self.task_id:self.task_id + 1]); r += 1
+        if n_prompt:
+            lm_input[r:r + n_prompt].copy_(K.gather(self.speech_emb, prompt_speech_token))
+        return lm_input, L, n_text
+
+    @torch.inference_mode()
+    def inference_batch(self, requests, slots=8, max_token_text_ratio=20, min_token_text_ratio=2, mark_end=False):
+        """N requests on ONE decode loop (cv_lm1_batch_*): every step streams the weights once for all the requests in flight.  No counterpart in the reference, whose
+        TransformerLM.inference (llm/llm.py:162-223) is batch-1; each request's tokens are exactly those of `inference` on it alone.
+        requests: a list of the keyword dicts `inference` takes (a dict's own max_token_text_ratio / min_token_text_ratio win over the arguments here).  Yields
+        (request index, tokens of one decode chunk); mark_end: also (request index, None) when a request has ended.  More requests than `slots` (1..8): a slot takes the
+        next request of the list when its sequence finishes.  Request i draws from the seed it would have had, had the requests gone through `inference` one after
+        another in list order.  Needs the device sampler and the fused step: the batch has no host-sampler or launch-per-operator form."""
+        if not (isinstance(self.sampling, str) and self.fused_step):
+            raise RuntimeError("TransformerLM.inference_batch needs the device sampler (sampling = 'greedy' or 'ras') and the fused decode step; "
+                               "this object has sampling=%r, fused_step=%r - use inference() per request" % (self.sampling, self.fused_step))
+        if not 1 <= int(slots) <= 8:
+            raise ValueError("TransformerLM.inference_batch: 1..8 slots, not %r" % (slots,))
+        from .llm import SamplingC
+        jobs = []                                                    # (index, request, min_len, max_len, seed) in list order
+        with self.lock:
+            for i, kw in enumerate(requests):
+                n_text = int(kw["text"].shape[1])
+                lo = int(n_text * kw.get("min_token_text_ratio", min_token_text_ratio))
+                hi = int(n_text * kw.get("max_token_text_ratio", max_token_text_ratio))
+                if hi > 0:                                           # (a request with no token budget yields nothing, as in `inference`)
+                    self._request += 1
+                    jobs.append((i, kw, lo, hi, self.seed + self._request))
+                elif mark_end:
+                    jobs.append((i, None, 0, 0, 0))
+        nb = max(1, min(int(slots), sum(1 for j in jobs if j[1] is not None)))
+        with self._pool_lock:
+            step = self._loop_steps.pop() if self._loop_steps else None
+        live = {}                                                    # slot -> [index, state, max_len, tokens yielded]
+        try:
+            with self.lock:
+                if step is None:
+                    step = self.llm.make_step(self.decoder, bf16=self.w16)
+                    for name, value in self._step_options.items():
+                        step.lib.cv_lm1_set_option(step.h, name.encode(), C.c_int32(value))
+                self.llm.batch_begin(step, nb)
+            jobs.reverse()
+            while jobs or live:
+                ended = []
+                with self.lock:
+                    for slot in range(nb):
+                        while slot not in live and jobs:
+                            i, kw, lo, hi, seed = jobs.pop()
+                            if kw is None:
+                                ended.append(i)
+                                continue
+                            lm_input, L, _ = self._lm_input(kw["text"], kw["prompt_text"], kw["prompt_speech_token"], kw["embedding"])
+                            _, state = self.llm.forward_chunk(lm_input[:L - 1], None)      # prefill: all rows but the last, exactly as `inference`
+                            sp = SamplingC(1 if self.sampling == "ras" else 0, self.eos_token, 1, lo, hi, 0.8, 25, 10, 0.1, seed, 1 if self._uniforms is not None else 0)
+                            self.llm.batch_open(step, slot, lm_input[L - 1:L].contiguous(), state, sp, self.speech_emb, self._uniforms)
+                            live[slot] = [i, state, hi, 0]
+                    out = {}
+                    if live:
+                        n = min([self.decode_chunk] + [r[2] - r[3] for r in live.values()])      # no slot is stepped past the rows reserved for it
+                        out = self.llm.batch_steps(step, {slot: r[1] for slot, r in live.items()}, n)
+                    chunks = []
+                    for slot, (toks, fin) in sorted(out.items()):
+                        r = live[slot]
+                        r[3] += len(toks)
+                        if toks:
+                            chunks.append((r[0], toks))
+                        if fin or r[3] >= r[2]:
+                            self.llm.batch_release(step, slot)
+                            ended.append(r[0])
+                            del live[slot]
+                for c in chunks:
+                    yield c
+                if mark_end:
+                    for i in ended:
+                        yield i, None
+        finally:                                                     # also on GeneratorExit: an abandoned batch frees its slots and gives its handle back
+            if step is not None:
+                with self.lock:
+                    for slot in list(live):
+                        self.llm.batch_release(step, slot)
+                step.bound = None
+                with self._pool_lock:
+                    self._loop_steps.append(step)
+
     @torch.inference_mode()
     def inference(self, text, text_len, prompt_text, prompt_text_len, prompt_speech_token, prompt_speech_token_len, embedding,
                   sampling=25, max_token_text_ratio=20, min_token_text_ratio=2, uuid=""):
         # The stage lock is taken PER STEP / PER CHUNK, never across a yield (ADVICE r3): a request's state is its own (_KVState, the recorded step with its buffers,
         # and - device loop - a cv_lm1 handle of its own from the pool), so another request may prefill or step between two of this one's tokens, and a consumer that
         # stops reading blocks nobody.
-        K, D = self.k, self.llm_input_size
+        K = self.k
         with self.lock:
-            ids = torch.cat([prompt_text, text], dim=1).reshape(-1).to(torch.int32)
-            n_text, n_prompt = int(text.shape[1]), int(prompt_speech_token.shape[1])
-            has_spk = embedding.shape[0] != 0
-            L = 1 + int(has_spk) + ids.numel() + 1 + n_prompt
-            lm_input = K.new(L, D)                                  # [sos | speaker | encoded text | task id | prompt speech tokens]
-            r = 0
-            lm_input[r:r + 1].copy_(self.llm_emb[self.sos:self.sos + 1]); r += 1
-            if has_spk:
-                e = torch.nn.functional.normalize(embedding.float().cpu(), dim=1)     # 192 numbers: normalised on the host
-                K.linear(K.put(e), self.spk_affine, 1, out=lm_input[r:]); r += 1
-            enc = self.encode_text(ids)
-            lm_input[r:r + ids.numel()].copy_(enc); r += ids.numel()
-            lm_input[r:r + 1].copy_(self.llm_emb[self.task_id:self.task_id + 1]); r += 1
-            if n_prompt:
-                lm_input[r:r + n_prompt].copy_(K.gather(self.speech_emb, prompt_speech_token))
+            lm_input, L, n_text = self._lm_input(text, prompt_text, prompt_speech_token, embedding)
         min_len, max_len = int(n_text * min_token_text_ratio), int(n_text * max_token_text_ratio)
         if isinstance(self.sampling, str) and self.fused_step and max_len > 0 and L >= 2:
             # the loop on the device: prefill all rows but the last through the chunk path, then the last row is the loop's first input
@@ -981,3 +1117,52 @@ class CosyVoiceModel(C1.CosyVoiceModel):
         self.llm = TransformerLM(ld(llm_model), lib=lib, weight_dtype=torch.bfloat16 if fp16 else None, **{k: kw[k] for k in ("text_heads", "llm_heads") if k in kw})
         self.flow = MaskedDiffWithXvec(ld(flow_model), lib=lib, precision="bf16" if fp16 else "fp32", **{k: kw[k] for k in ("enc_heads", "est_heads", "input_frame_rate") if k in kw})
         self.hift = HiFTGenerator({k.replace("generator.", ""): v for k, v in ld(hift_model).items()}, hift_cfg or cv1()[1], lib=lib, **kw.get("hift", {}))
+
+    def tts_batch(self, requests, slots=8, speed=1.0):
+        """Offline synthesis of several requests whose speech tokens come from ONE batched decode loop (TransformerLM.inference_batch: one weight stream per token for
+        all of them; the reference runs one `tts` - cli/model.py:175-242 - per request).  requests: a list of dicts of `tts`'s keyword arguments (text, llm_embedding,
+        flow_embedding, prompt_text, llm_prompt_speech_token, flow_prompt_speech_token, prompt_speech_feat).  Each request that finishes goes through the offline
+        `token2wav` path on its own (the U-Net flow is batch-1); yields (index, {'tts_speech': [1, S] fp32 cpu}) in the order the requests finish."""
+        import uuid as uuid_mod
+        e0, t = torch.zeros(1, 0, dtype=torch.int32), (lambda n: torch.tensor([n], dtype=torch.int32))
+        get = lambda r, k, d: r[k] if k in r else d
+        lm_reqs = []
+        for r in requests:
+            pt, ps = get(r, "prompt_text", e0), get(r, "llm_prompt_speech_token", e0)
+            lm_reqs.append(dict(text=r["text"], text_len=t(r["text"].shape[1]), prompt_text=pt, prompt_text_len=t(pt.shape[1]), prompt_speech_token=ps,
+                                prompt_speech_token_len=t(ps.shape[1]), embedding=get(r, "llm_embedding", torch.zeros(0, 192)),
+                                **{k: r[k] for k in ("max_token_text_ratio", "min_token_text_ratio") if k in r}))
+        uuids = [str(uuid_mod.uuid1()) for _ in requests]
+        with self.lock:
+            for u in uuids:
+                self.tts_speech_token_dict[u], self.llm_end_dict[u] = [], False
+                self.hift_cache_dict[u] = None
+                self.mel_overlap_dict[u] = torch.zeros(1, 80, 0)
+                self.flow_cache_dict[u] = torch.zeros(1, 80, 0, 2)
+        gen = self.llm.inference_batch(lm_reqs, slots=slots, mark_end=True)
+        silent = [0] * len(requests)
+        try:
+            for i, toks in gen:
+                u = uuids[i]
+                if toks is not None:
+                    for tok in toks:                                 # llm_job's filter of runs of silent tokens (cli/model.py:101-115)
+                        if tok in self.silent_tokens:
+                            silent[i] += 1
+                            if silent[i] > 5:
+                                continue
+                        else:
+                            silent[i] = 0
+                        self.tts_speech_token_dict[u].append(tok)
+                    continue
+                self.llm_end_dict[u] = True
+                r = requests[i]
+                allt = torch.tensor(self.tts_speech_token_dict[u], dtype=torch.int64).reshape(1, -1)
+                wav = self.token2wav(token=allt, prompt_token=get(r, "flow_prompt_speech_token", e0), prompt_feat=get(r, "prompt_speech_feat", torch.zeros(1, 0, 80)),
+                                     embedding=get(r, "flow_embedding", torch.zeros(0, 192)), uuid=u, finalize=True, speed=speed).cpu()
+                yield i, {"tts_speech": wav}
+        finally:
+            gen.close()
+            with self.lock:
+                for u in uuids:
+                    for d in (self.tts_speech_token_dict, self.llm_end_dict, self.mel_overlap_dict, self.hift_cache_dict, self.flow_cache_dict, self._cond, self._llm_error):
+                        d.pop(u, None)

@@ -325,10 +325,211 @@ static __global__ __launch_bounds__(64 * NW) void lm1_gemv16_kernel(Lm1GemvArgs 
     }
 }
 
+// ---- lock-step batched decode (cv_lm1_batch_*): the same products for up to LM1_MAX_SLOTS sequences, every weight row read ONCE per step ---------------------------
+// A lane owns the (row, k-subset) it owns in the single-sequence kernel and carries one accumulator per slot: for every slot the products, their order, the 16-lane
+// reduction and the combine of the waves' partial sums are those of the kernel gemv() picks for the same (N, K, dtype, prologue), so a slot's output has the bits of
+// cv_lm1_step on that sequence alone - whatever the slot count and whichever slot it sits in.  What differs is the schedule: a lane's WHOLE share of its row is
+// requested up front and kept in registers (at most 16 steps: K <= 4096 over 4 waves), and the slots' input vectors go through LDS G at a time - all of them when
+// K <= 1024 (every LayerNorm / merge prologue), two per pass for the K <= 4096 products (static LDS: 8 x 16.6 KB do not fit) - with a barrier between the passes,
+// which does not touch any lane's order of accumulation.  A slot whose flag (Lm1Dyn::pad0) is clear is skipped: no pointer of it is read, nothing of it is written.
+constexpr int LM1_MAX_SLOTS = 8;
+struct Lm1BGemvArgs {
+    Lm1GemvArgs a;                             // slot 0's x / res / y; the matrix, bias, gamma / beta are shared; a.dyn / a.st are unused (dyns / sts below)
+    long long sx, sres, sy;                    // floats between two slots' x / res / y
+    Lm1Dyn* dyns;                              // [nb]: position, cache rows, tables, flag (pad0 != 0: the slot takes part in the step)
+    const DecodeState* sts;                    // [nb] (a.set_pos == -2: block 0 publishes every slot's position)
+    int nb;
+};
+
+static __device__ __forceinline__ void lm1b_publish(const Lm1BGemvArgs& q) {
+    if (q.a.set_pos == -2 && blockIdx.x == 0 && (int)threadIdx.x < q.nb) q.dyns[threadIdx.x].pos = q.sts[threadIdx.x].pos;
+}
+
+// lm1_gemv_kernel<U, NW, W16> for NBT slots; S: steps of a lane's share held in registers (4: U = 4 forms, steps <= 16; 8: NW = 8; 16: U = 8, NW = 4), KW: longest input.
+template <int S, int NW, bool W16, int NBT, int G, int KW>
+static __global__ __launch_bounds__(64 * NW) void lm1_gemvb_kernel(Lm1BGemvArgs q) {
+    constexpr int XS = KW + 64;
+    __shared__ __attribute__((aligned(16))) float xs[G * XS];
+    __shared__ float part[NBT][NW][4];
+    __shared__ float mw[G][256];
+    const Lm1GemvArgs& p = q.a;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4, sub = lane & 15;
+    const int steps = (p.Kp + 63) / 64;
+    lm1b_publish(q);
+    bool on[NBT];
+#pragma unroll
+    for (int s = 0; s < NBT; ++s) on[s] = s < q.nb && q.dyns[min(s, q.nb - 1)].pad0 != 0;
+    const int row0 = (int)blockIdx.x * 4 + grp;
+    const int s0 = wave * steps / NW, s1 = (wave + 1) * steps / NW;
+    using raw_t = typename std::conditional<W16, lm1_u32x2, v4f>::type;
+    raw_t w[S];
+    auto load_all = [&] {
+        const long long ro = (long long)min(row0, p.N - 1) * p.ldw;
+#pragma unroll
+        for (int u = 0; u < S; ++u) {                           // unconditional loads (clamped step)
+            const int k = min(min(s0 + u, max(s1 - 1, 0)) * 64 + sub * 4, p.Kp - 4);
+            if constexpr (W16) w[u] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x2*>(reinterpret_cast<const unsigned short*>(p.W) + ro + k));
+            else w[u] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p.W + ro + k));
+        }
+    };
+    auto wide = [](const raw_t& r) -> v4f {
+        if constexpr (W16) return (v4f){__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16), __uint_as_float(r[1] & 0xffff0000u)};
+        else return r;
+    };
+    if (!on[0]) load_all();                                     // (slot 0's prologue requests them behind its own small operands, like the single-sequence kernel)
+    float acc[NBT];
+#pragma unroll
+    for (int s = 0; s < NBT; ++s) acc[s] = 0.f;
+#pragma unroll
+    for (int p0 = 0; p0 < NBT; p0 += G) {
+        if (p0 > 0) __syncthreads();                            // every lane is done with the previous pass's vectors
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int sl = p0 + g;
+            if (on[sl]) {
+                Lm1GemvArgs ps = p;
+                ps.x = p.x + sl * q.sx;
+                lm1_gemv_prologue<NW>(ps, xs + g * XS, mw[g], steps, [&] { if (sl == 0) load_all(); });
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < S; ++u) {
+            if (s0 + u < s1) {
+                const v4f wf = wide(w[u]);
+                const int k = (s0 + u) * 64 + sub * 4;
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    if (on[p0 + g]) {
+                        const float4 x = *reinterpret_cast<const float4*>(&xs[g * XS + k]);
+                        float a = acc[p0 + g];
+                        a += wf[0] * x.x; a += wf[1] * x.y; a += wf[2] * x.z; a += wf[3] * x.w;
+                        acc[p0 + g] = a;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NBT; ++s) {
+        if (on[s]) {
+            const float a = group16_sum(acc[s]);
+            if (sub == 0) part[s][wave][grp] = a;
+        }
+    }
+    __syncthreads();
+    if (wave != 0 || sub >= q.nb || sub >= NBT) return;         // lane `sub` of the group finishes slot `sub`
+    const int sl = sub, n = row0;
+    if (n >= p.N || q.dyns[sl].pad0 == 0) return;
+    float v = ((part[sl][0][grp] + part[sl][1][grp]) + part[sl][2][grp]) + part[sl][3][grp];
+    if (NW == 8) v = (((v + part[sl][4 % NW][grp]) + part[sl][5 % NW][grp]) + part[sl][6 % NW][grp]) + part[sl][7 % NW][grp];
+    if (p.bias) v += p.bias[n];
+    v = apply_act(p.act, v, 0.f);
+    if (p.res) v += p.res[sl * q.sres + n];
+    float* y = p.layer >= 0 ? q.dyns[sl].rows[p.layer] + (long long)q.dyns[sl].pos * p.N : p.y + sl * q.sy;
+    y[n] = v;
+}
+
+// lm1_gemv16_kernel<W16, STEPS, 1, NW, KSPLIT> for NBT slots (its weights already sit in registers for the whole row share).
+template <bool W16, int STEPS, int NW, bool KSPLIT, int NBT, int G, int KW>
+static __global__ __launch_bounds__(64 * NW) void lm1_gemv16b_kernel(Lm1BGemvArgs q) {
+    constexpr int SK = W16 ? 128 : 64, LK = W16 ? 8 : 4;
+    constexpr int XS = KW + 64;
+    __shared__ __attribute__((aligned(16))) float xs[G * XS];
+    __shared__ float part[NBT][NW][4];
+    __shared__ float mw[G][256];
+    const Lm1GemvArgs& p = q.a;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4, sub = lane & 15;
+    const int steps = p.Kp / SK;
+    lm1b_publish(q);
+    bool on[NBT];
+#pragma unroll
+    for (int s = 0; s < NBT; ++s) on[s] = s < q.nb && q.dyns[min(s, q.nb - 1)].pad0 != 0;
+    const int row0 = KSPLIT ? (int)blockIdx.x * 4 + grp : ((int)blockIdx.x * NW + wave) * 4 + grp;
+    const int s0 = KSPLIT ? wave * steps / NW : 0, s1 = KSPLIT ? (wave + 1) * steps / NW : steps;
+    lm1_u32x4 w[STEPS];
+    auto load_all = [&] {
+        const long long ro = (long long)min(row0, p.N - 1) * p.ldw + sub * LK;
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) {
+            const long long k = ro + (long long)min(s0 + s, max(s1 - 1, 0)) * SK;
+            if constexpr (W16) w[s] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x4*>(reinterpret_cast<const unsigned short*>(p.W) + k));
+            else w[s] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x4*>(p.W + k));
+        }
+    };
+    if (!on[0]) load_all();
+    float acc[NBT];
+#pragma unroll
+    for (int s = 0; s < NBT; ++s) acc[s] = 0.f;
+#pragma unroll
+    for (int p0 = 0; p0 < NBT; p0 += G) {
+        if (p0 > 0) __syncthreads();
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int sl = p0 + g;
+            if (on[sl]) {
+                Lm1GemvArgs ps = p;
+                ps.x = p.x + sl * q.sx;
+                lm1_gemv_prologue<NW>(ps, xs + g * XS, mw[g], steps * SK / 64, [&] { if (sl == 0) load_all(); });
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) {
+            if (s0 + s < s1) {
+                const lm1_u32x4 u = w[s];
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    if (on[p0 + g]) {
+                        const float* xg = &xs[g * XS + (s0 + s) * SK + sub * LK];
+                        const float4 xa = *reinterpret_cast<const float4*>(xg);
+                        float a = acc[p0 + g];
+                        if constexpr (W16) {
+                            const float4 xb = *reinterpret_cast<const float4*>(xg + 4);
+                            a += __uint_as_float(u[0] << 16) * xa.x;          a += __uint_as_float(u[0] & 0xffff0000u) * xa.y;
+                            a += __uint_as_float(u[1] << 16) * xa.z;          a += __uint_as_float(u[1] & 0xffff0000u) * xa.w;
+                            a += __uint_as_float(u[2] << 16) * xb.x;          a += __uint_as_float(u[2] & 0xffff0000u) * xb.y;
+                            a += __uint_as_float(u[3] << 16) * xb.z;          a += __uint_as_float(u[3] & 0xffff0000u) * xb.w;
+                        } else {
+                            a += __uint_as_float(u[0]) * xa.x; a += __uint_as_float(u[1]) * xa.y; a += __uint_as_float(u[2]) * xa.z; a += __uint_as_float(u[3]) * xa.w;
+                        }
+                        acc[p0 + g] = a;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NBT; ++s) if (on[s]) acc[s] = group16_sum(acc[s]);
+    if constexpr (KSPLIT) {
+#pragma unroll
+        for (int s = 0; s < NBT; ++s) if (on[s] && sub == 0) part[s][wave][grp] = acc[s];
+        __syncthreads();
+        if (wave != 0) return;
+#pragma unroll
+        for (int s = 0; s < NBT; ++s) if (on[s]) { float t = 0.f; for (int ww = 0; ww < NW; ++ww) t += part[s][ww][grp]; acc[s] = t; }
+    }
+    if (sub != 0 || row0 >= p.N) return;
+    const int n = row0;
+#pragma unroll
+    for (int s = 0; s < NBT; ++s) {
+        if (on[s]) {
+            float v = acc[s];
+            if (p.bias) v += p.bias[n];
+            v = apply_act(p.act, v, 0.f);
+            if (p.res) v += p.res[s * q.sres + n];
+            float* y = p.layer >= 0 ? q.dyns[s].rows[p.layer] + (long long)q.dyns[s].pos * p.N : p.y + s * q.sy;
+            y[n] = v;
+        }
+    }
+}
+
 // LayerNorm -> activation -> * scale of one row (the input layer's norm; its output is the residual stream, so it is materialised)
-struct Lm1NormArgs { const float* x; float* y; const float* g; const float* b; float eps, scale; int C, act; };
+// (batched decode: workgroup b is slot b - sx / sy floats between the slots' rows, `dyns` their flags; the single step launches one workgroup with dyns = null)
+struct Lm1NormArgs { const float* x; float* y; const float* g; const float* b; float eps, scale; int C, act; long long sx = 0, sy = 0; const Lm1Dyn* dyns = nullptr; };
 static __global__ __launch_bounds__(64) void lm1_norm_kernel(Lm1NormArgs p) {
     const int lane = threadIdx.x;
+    if (p.dyns) { if (p.dyns[blockIdx.x].pad0 == 0) return; p.x += (long long)blockIdx.x * p.sx; p.y += (long long)blockIdx.x * p.sy; }
     float4 v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -365,11 +566,13 @@ static __global__ __launch_bounds__(64) void lm1_norm_kernel(Lm1NormArgs p) {
 // 16 * LM1_AU * LM1_SPLITS = 512 keys the whole context is requested before the first score exists (the kernel is a chain of latencies, not of bytes); every
 // group keeps a running (m, l, acc) over its keys, the 16 groups merge through LDS.
 constexpr int LM1_AU = 4;
-struct Lm1AttnArgs { const Lm1Dyn* dyn; int layer, d, heads; float scale; float* part; };
+// (batched decode: blockIdx.z is the slot - its own Lm1Dyn and its own block of `part`, slot_part floats further; an inactive slot returns at once)
+struct Lm1AttnArgs { const Lm1Dyn* dyn; int layer, d, heads; float scale; float* part; long long slot_part = 0; int batched = 0; };
 static __global__ __launch_bounds__(256) void lm1_attn_kernel(Lm1AttnArgs p) {
     __shared__ float gm[16], gl[16];
     __shared__ float gacc[16][64];
     const int h = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, sub = tid & 15, kg = tid >> 4;
+    if (p.batched) { p.dyn += blockIdx.z; p.part += (long long)blockIdx.z * p.slot_part; if (p.dyn->pad0 == 0) return; }
     const int pos = p.dyn->pos, n = pos + 1, d = p.d;
     const int per = (n + LM1_SPLITS - 1) / LM1_SPLITS, j0 = min(n, s * per), j1 = min(n, j0 + per), cnt = j1 - j0;
     const float* rows = p.dyn->rows[p.layer];
@@ -435,6 +638,14 @@ static __global__ __launch_bounds__(256) void lm1_attn_kernel(Lm1AttnArgs p) {
 }
 
 static __global__ void lm1_bind_kernel(Lm1Dyn* dyn, Lm1Dyn v) { if (threadIdx.x == 0 && blockIdx.x == 0) *dyn = v; }
+// a slot of the batched decode: rebinding (a grown cache) keeps the slot's flag and position; the flag is set when a request is parked and cleared when the slot is freed
+static __global__ void lm1_bind_slot_kernel(Lm1Dyn* dyn, Lm1Dyn v) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) { v.pad0 = dyn->pad0; v.pos = dyn->pos; *dyn = v; }
+}
+static __global__ void lm1_slot_flag_kernel(Lm1Dyn* dyn, DecodeState* st, int on) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) { dyn->pad0 = on; if (!on) st->done = 1; }
+}
+static __global__ void lm1_advance_slots_kernel(DecodeState* st, int nb) { if ((int)threadIdx.x < nb && !st[threadIdx.x].done) st[threadIdx.x].pos += 1; }
 
 struct Lm1Layer {
     const float *ln1_g, *ln1_b, *w_qkv, *b_qkv, *w_out, *b_out, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2;
@@ -463,6 +674,17 @@ struct cv_lm1 {
     hipStream_t own_stream = nullptr;          // a NULL stream argument means this (blocking) stream: it orders itself against the legacy default stream, and it can be captured
     int use_graph = 0, bound = 0;              // measured on the MI355X (profiles/r4_cv1_fused_step_timing.txt): the replayed graph is 3 % SLOWER per token than the same 72 launches issued eagerly
     long long steps = 0, graph_replays = 0;
+    // the lock-step batched decode (cv_lm1_batch_*): per-slot copies of everything above that belongs to ONE sequence
+    struct Slot { int bound = 0, open = 0, cap = 0, returned = 0; DecodeState host{}; };
+    struct Batch {
+        int nb = 0, tok_cap = 0, uni_cap = 0;
+        Slot slots[LM1_MAX_SLOTS];
+        DevBuf dyns, sts, sps, tokens, uniforms, xin, logits, x0, x1, h, ff, part;
+        const float* emb_table = nullptr;
+        std::vector<DecodeState> host_states; std::vector<int> host_tokens;
+        hipStream_t stream = nullptr;
+    } batch;
+    long long batch_steps = 0;
     ~cv_lm1() { if (graph) (void)hipGraphExecDestroy(graph); if (own_stream) (void)hipStreamDestroy(own_stream); }
 };
 
@@ -524,6 +746,91 @@ void step_body(cv_lm1* m, float* logits, hipStream_t s) {
         gemv(m, LM1_PRO_NONE, ff, nullptr, nullptr, 0.f, L.w2, H.w2, L.b2, x1, x0, -1, -1, d, m->ffn, ACT_NONE, s);
     }
     gemv(m, LM1_PRO_LN, x0, m->after_g, m->after_b, 1e-5f, m->dec_w, m->dec_w16, m->dec_b, nullptr, logits, -1, -1, m->n_out, d, ACT_NONE, s);
+}
+
+// ---- the batched step ---------------------------------------------------------------------------------------------------------------------------------------
+// gemv() for the slots of the batch: the SAME choice of kernel form per (N, K, dtype, prologue) - that is what keeps a slot's bits those of the single step.
+template <int NBT>
+void gemvb_n(cv_lm1* m, const Lm1BGemvArgs& q, bool h16, int pro, int N, int K, hipStream_t s) {
+    constexpr int GA = NBT, GB = NBT < 2 ? NBT : 2;            // slots' vectors in LDS at a time: all (K <= 1024) / two (K <= 4096)
+    const int kp = kp_of(K), steps = (kp + 63) / 64;
+    if (h16 && m->wide16 && kp % 128 == 0) {
+        const int st = kp / 128;
+        if (st <= 8 && N >= 2048) { hipLaunchKernelGGL((lm1_gemv16b_kernel<true, 8, 4, false, NBT, GA, 1024>), dim3((unsigned)((N + 15) / 16)), dim3(256), 0, s, q); return; }
+        if (st <= 8) { hipLaunchKernelGGL((lm1_gemv16b_kernel<true, 2, 4, true, NBT, GA, 1024>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, q); return; }
+        if (st <= 32 && pro == LM1_PRO_NONE) { hipLaunchKernelGGL((lm1_gemv16b_kernel<true, 4, 8, true, NBT, GB, LM1_MAX_K>), dim3((unsigned)((N + 3) / 4)), dim3(512), 0, s, q); return; }
+    }
+    if (!h16 && m->wide32 && kp % 64 == 0 && kp <= 1024 && N >= 2048) {
+        hipLaunchKernelGGL((lm1_gemv16b_kernel<false, 16, 4, false, NBT, GA, 1024>), dim3((unsigned)((N + 15) / 16)), dim3(256), 0, s, q); return;
+    }
+    const dim3 grid((unsigned)((N + 3) / 4));
+    if (h16) {
+        if (steps <= 16) hipLaunchKernelGGL((lm1_gemvb_kernel<4, 4, true, NBT, GA, 1024>), grid, dim3(256), 0, s, q);
+        else if (pro == LM1_PRO_NONE && N <= 2048) hipLaunchKernelGGL((lm1_gemvb_kernel<8, 8, true, NBT, GB, LM1_MAX_K>), grid, dim3(512), 0, s, q);
+        else hipLaunchKernelGGL((lm1_gemvb_kernel<16, 4, true, NBT, GB, LM1_MAX_K>), grid, dim3(256), 0, s, q);
+        return;
+    }
+    if (steps <= 16) hipLaunchKernelGGL((lm1_gemvb_kernel<4, 4, false, NBT, GA, 1024>), grid, dim3(256), 0, s, q);
+    else if (pro == LM1_PRO_NONE && N <= 2048) hipLaunchKernelGGL((lm1_gemvb_kernel<8, 8, false, NBT, GB, LM1_MAX_K>), grid, dim3(512), 0, s, q);
+    else hipLaunchKernelGGL((lm1_gemvb_kernel<16, 4, false, NBT, GB, LM1_MAX_K>), grid, dim3(256), 0, s, q);
+}
+
+void gemvb(cv_lm1* m, int pro, const float* x, long long sx, const float* g, const float* b, float eps, const float* W, const void* W16, const float* bias, const float* res, long long sres,
+           float* y, long long sy, int layer, int set_pos, int N, int K, int act, hipStream_t s) {
+    CV_CHECK(K % 4 == 0 && K <= LM1_MAX_K && (pro != LM1_PRO_LN || K <= 1024), "cv_lm1: a GEMV input of up to 4096 floats (1024 under the LayerNorm prologue), K % 4 == 0");
+    cv_lm1::Batch& B = m->batch;
+    const bool h16 = m->w16 && W16 != nullptr;
+    Lm1BGemvArgs q{};
+    q.a = Lm1GemvArgs{x, g, b, eps, h16 ? reinterpret_cast<const float*>(W16) : W, (long long)kp_of(K), bias, res, y, nullptr, layer, set_pos, nullptr, N, K, kp_of(K), act, pro};
+    q.sx = sx; q.sres = sres; q.sy = sy; q.dyns = B.dyns.as<Lm1Dyn>(); q.sts = B.sts.as<DecodeState>(); q.nb = B.nb;
+    if (B.nb == 1) gemvb_n<1>(m, q, h16, pro, N, K, s);
+    else if (B.nb == 2) gemvb_n<2>(m, q, h16, pro, N, K, s);
+    else if (B.nb <= 4) gemvb_n<4>(m, q, h16, pro, N, K, s);
+    else gemvb_n<8>(m, q, h16, pro, N, K, s);
+}
+
+// one lock-step step of every active slot: the launches of cv_lm1_decode's step, each of them over the slots
+void batch_step(cv_lm1* m, hipStream_t s) {
+    cv_lm1::Batch& B = m->batch;
+    const int d = m->d, nb = B.nb;
+    const long long sp = (long long)m->heads * LM1_SPLITS * 66;
+    float* x0 = B.x0.as<float>(); float* x1 = B.x1.as<float>(); float* h = B.h.as<float>(); float* ff = B.ff.as<float>(); float* part = B.part.as<float>();
+    Lm1Dyn* dyns = B.dyns.as<Lm1Dyn>();
+    gemvb(m, LM1_PRO_NONE, B.xin.as<float>(), m->d_in, nullptr, nullptr, 0.f, m->embed_w, m->embed_w16, m->embed_b, nullptr, 0, h, d, -1, -2, d, m->d_in, ACT_NONE, s);
+    Lm1NormArgs na{h, x0, m->embed_g, m->embed_beta, 1e-5f, m->xscale, d, m->act};
+    na.sx = d; na.sy = d; na.dyns = dyns;
+    hipLaunchKernelGGL(lm1_norm_kernel, dim3(nb), dim3(64), 0, s, na);
+    for (int i = 0; i < m->n_layers; ++i) {
+        const Lm1Layer& L = m->L[i];
+        const cv_lm1::L16 H = m->w16 ? m->L16s[i] : cv_lm1::L16{};
+        gemvb(m, LM1_PRO_LN, x0, d, L.ln1_g, L.ln1_b, 1e-12f, L.w_qkv, H.w_qkv, L.b_qkv, nullptr, 0, nullptr, 0, i, -1, 4 * d, d, ACT_NONE, s);
+        Lm1AttnArgs aa{dyns, i, d, m->heads, 0.125f, part};
+        aa.slot_part = sp; aa.batched = 1;
+        hipLaunchKernelGGL(lm1_attn_kernel, dim3(m->heads, LM1_SPLITS, nb), dim3(256), 0, s, aa);
+        gemvb(m, LM1_PRO_MERGE, part, sp, nullptr, nullptr, 0.f, L.w_out, H.w_out, L.b_out, x0, d, x1, d, -1, -1, d, d, ACT_NONE, s);
+        gemvb(m, LM1_PRO_LN, x1, d, L.ln2_g, L.ln2_b, 1e-12f, L.w1, H.w1, L.b1, nullptr, 0, ff, m->ffn, -1, -1, m->ffn, d, m->act, s);
+        gemvb(m, LM1_PRO_NONE, ff, m->ffn, nullptr, nullptr, 0.f, L.w2, H.w2, L.b2, x1, d, x0, d, -1, -1, d, m->ffn, ACT_NONE, s);
+    }
+    gemvb(m, LM1_PRO_LN, x0, d, m->after_g, m->after_b, 1e-5f, m->dec_w, m->dec_w16, m->dec_b, nullptr, 0, B.logits.as<float>(), m->n_out, -1, -1, m->n_out, d, ACT_NONE, s);
+    SampleArgs sa{};
+    sa.logits = B.logits.as<float>(); sa.V = m->n_out; sa.sp = B.sps.as<SampleParams>(); sa.uniforms = B.uniforms.as<float>();
+    sa.st = B.sts.as<DecodeState>(); sa.tokens = B.tokens.as<int>(); sa.max_tokens = B.tok_cap;
+    sa.emb_table_f32 = B.emb_table; sa.emb_dim = m->d_in; sa.h_out = B.xin.as<float>();
+    sa.slot_logits = m->n_out; sa.slot_uniforms = B.uni_cap; sa.slot_tokens = B.tok_cap; sa.slot_h = m->d_in;
+    hipLaunchKernelGGL(sample_kernel, dim3(nb), dim3(1024), 0, s, sa);
+    hipLaunchKernelGGL(lm1_advance_slots_kernel, dim3(1), dim3(64), 0, s, sa.st, nb);
+    ++m->batch_steps;
+}
+
+// a per-slot array grows (a request with a longer token budget than any before): the slots' contents move to the new pitch
+void grow_slots(DevBuf& buf, size_t old_pitch, size_t new_pitch, int nb, hipStream_t s) {
+    DevBuf fresh;
+    fresh.ensure(new_pitch * nb);
+    CV_HIP(hipMemsetAsync(fresh.p, 0, new_pitch * nb, s));
+    for (int i = 0; i < nb && old_pitch; ++i)
+        CV_HIP(hipMemcpyAsync(static_cast<char*>(fresh.p) + i * new_pitch, static_cast<char*>(buf.p) + i * old_pitch, old_pitch, hipMemcpyDeviceToDevice, s));
+    CV_HIP(hipStreamSynchronize(s));
+    std::swap(buf.p, fresh.p); std::swap(buf.bytes, fresh.bytes);
 }
 
 }  // namespace
@@ -688,11 +995,159 @@ int cv_lm1_decode(cv_lm1* m, int32_t n_steps, int32_t* out_tokens, int32_t* n_ou
     });
 }
 
+// ---- lock-step batched decode (no counterpart in the reference: TransformerLM.inference, llm/llm.py:162-223, is batch-1; the Qwen2 path's cv_llm_batch_* is the model) ----
+// Up to LM1_MAX_SLOTS requests advance one token per step and every matrix of the step is streamed once for all of them; a slot's tokens, logits and cache rows are
+// those of cv_lm1_decode on that request alone.  Slots are bound (cache rows, tables), opened (first input row, position, sampling parameters) and released one by
+// one, also between two cv_lm1_batch_decode calls - that is how a finished request's slot takes the next request.
+int cv_lm1_batch_begin(cv_lm1* m, int32_t nb, void* stream) {
+    return guarded([&] {
+        CV_CHECK(m, "cv_lm1_batch_begin: null handle");
+        CV_CHECK(nb >= 1 && nb <= LM1_MAX_SLOTS, "cv_lm1_batch_begin: 1..8 slots");
+        CV_CHECK(m->n_out <= 8192, "cv_lm1_batch_begin: the device sampler holds at most 8192 logits");
+        hipStream_t s = resolve(m, stream);
+        cv_lm1::Batch& B = m->batch;
+        CV_HIP(hipStreamSynchronize(s));
+        const size_t n = (size_t)nb;
+        B.dyns.ensure(n * sizeof(Lm1Dyn)); B.sts.ensure(n * sizeof(DecodeState)); B.sps.ensure(n * sizeof(SampleParams));
+        B.xin.ensure(n * m->d_in * 4); B.logits.ensure(n * m->n_out * 4); B.x0.ensure(n * m->d * 4); B.x1.ensure(n * m->d * 4); B.h.ensure(n * m->d * 4);
+        B.ff.ensure(n * m->ffn * 4); B.part.ensure(n * m->heads * LM1_SPLITS * 66 * 4);
+        if (B.nb != nb) { B.tok_cap = 0; B.uni_cap = 0; }       // (the per-slot pitches belong to a slot count)
+        B.nb = nb; B.emb_table = nullptr; B.stream = s;
+        B.host_states.assign(n, DecodeState{});
+        for (int i = 0; i < LM1_MAX_SLOTS; ++i) B.slots[i] = cv_lm1::Slot{};
+        std::vector<DecodeState> st(n);
+        for (auto& e : st) { e = DecodeState{}; e.done = 1; e.stop_token = -1; }
+        CV_HIP(hipMemsetAsync(B.dyns.p, 0, n * sizeof(Lm1Dyn), s));
+        CV_HIP(hipMemsetAsync(B.sps.p, 0, n * sizeof(SampleParams), s));
+        CV_HIP(hipMemsetAsync(B.logits.p, 0, n * m->n_out * 4, s));
+        CV_HIP(hipMemcpyAsync(B.sts.p, st.data(), n * sizeof(DecodeState), hipMemcpyHostToDevice, s));
+        CV_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int cv_lm1_batch_bind(cv_lm1* m, int32_t slot, float* const* rows, const float* const* tabs, int32_t n_tab, int32_t cap, void* stream) {
+    return guarded([&] {
+        CV_CHECK(m && rows && tabs, "cv_lm1_batch_bind: null argument");
+        CV_CHECK(m->batch.nb > 0, "cv_lm1_batch_bind: cv_lm1_batch_begin first");
+        CV_CHECK(slot >= 0 && slot < m->batch.nb, "cv_lm1_batch_bind: slot out of range");
+        CV_CHECK(cap >= 1 && cap <= LM1_SPLITS * LM1_MAX_KEYS_PER_SPLIT, "cv_lm1_batch_bind: a cache of up to 32768 positions");
+        CV_CHECK(n_tab >= cap, "cv_lm1_batch_bind: the relative-position tables must cover the cache (n_tab >= cap)");
+        cv_lm1::Slot& S = m->batch.slots[slot];
+        CV_CHECK(!S.open || S.host.done || S.host.pos < cap, "cv_lm1_batch_bind: the new cache ends before the slot's position");
+        Lm1Dyn v{};
+        v.n_tab = n_tab;
+        for (int i = 0; i < m->n_layers; ++i) {
+            CV_CHECK(rows[i] && tabs[i] && aligned16(rows[i]) && aligned16(tabs[i]), "cv_lm1_batch_bind: cache / table buffers present and 16B aligned");
+            v.rows[i] = rows[i]; v.tabs[i] = tabs[i];
+        }
+        hipStream_t s = resolve(m, stream);
+        Lm1Dyn* dslot = m->batch.dyns.as<Lm1Dyn>() + slot;
+        hipLaunchKernelGGL(lm1_bind_slot_kernel, dim3(1), dim3(64), 0, s, dslot, v);
+        S.cap = cap; S.bound = 1; m->batch.stream = s;
+    });
+}
+
+int cv_lm1_batch_open(cv_lm1* m, int32_t slot, const float* x_row, int32_t pos, const cv_sampling* sp, const float* emb_table, int32_t max_tokens, const float* host_uniforms,
+                      int32_t n_uniforms, void* stream) {
+    return guarded([&] {
+        CV_CHECK(m && x_row && sp && emb_table && aligned16(x_row) && aligned16(emb_table), "cv_lm1_batch_open: null / unaligned argument");
+        cv_lm1::Batch& B = m->batch;
+        CV_CHECK(B.nb > 0, "cv_lm1_batch_open: cv_lm1_batch_begin first");
+        CV_CHECK(slot >= 0 && slot < B.nb, "cv_lm1_batch_open: slot out of range");
+        cv_lm1::Slot& S = B.slots[slot];
+        CV_CHECK(S.bound, "cv_lm1_batch_open: cv_lm1_batch_bind first");
+        CV_CHECK(!S.open, "cv_lm1_batch_open: the slot holds a request (cv_lm1_batch_release first)");
+        CV_CHECK(pos >= 0 && pos < S.cap && max_tokens >= 1, "cv_lm1_batch_open: position beyond the bound cache");
+        CV_CHECK(sp->max_len > 0 && sp->max_len <= max_tokens && sp->eos >= 0 && sp->eos + sp->n_stop <= m->n_out, "cv_lm1_batch_open: bad sampling parameters");
+        CV_CHECK(sp->mode == 0 || (sp->top_k > 0 && sp->top_k <= 64 && sp->win_size >= 0), "cv_lm1_batch_open: bad RAS parameters");
+        CV_CHECK(!sp->use_uniforms || (host_uniforms && n_uniforms >= 2), "cv_lm1_batch_open: use_uniforms needs the uniforms");
+        bool others = false;
+        for (int i = 0; i < B.nb; ++i) others = others || B.slots[i].open;
+        CV_CHECK(!others || B.emb_table == emb_table, "cv_lm1_batch_open: the slots of a batch share one embedding table");
+        hipStream_t s = resolve(m, stream);
+        if (max_tokens > B.tok_cap) { const int cap = std::max(max_tokens, 2 * B.tok_cap); grow_slots(B.tokens, (size_t)B.tok_cap * 4, (size_t)cap * 4, B.nb, s); B.tok_cap = cap; }
+        if (sp->use_uniforms && 2 * sp->max_len > B.uni_cap) {
+            const int cap = std::max(2 * sp->max_len, 2 * B.uni_cap); grow_slots(B.uniforms, (size_t)B.uni_cap * 4, (size_t)cap * 4, B.nb, s); B.uni_cap = cap;
+        }
+        B.host_tokens.resize((size_t)B.nb * B.tok_cap);
+        DecodeState st{}; st.pos = pos; st.stop_token = -1;
+        const SampleParams hp{sp->mode, sp->eos, sp->n_stop, sp->min_len, sp->max_len, sp->top_p, sp->top_k, sp->win_size, sp->tau_r, sp->use_uniforms, (unsigned long long)sp->seed};
+        CV_HIP(hipMemcpyAsync(B.sts.as<DecodeState>() + slot, &st, sizeof(st), hipMemcpyHostToDevice, s));
+        CV_HIP(hipMemcpyAsync(B.sps.as<SampleParams>() + slot, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
+        CV_HIP(hipMemcpyAsync(B.xin.as<float>() + (size_t)slot * m->d_in, x_row, (size_t)m->d_in * 4, hipMemcpyDeviceToDevice, s));
+        if (sp->use_uniforms)
+            CV_HIP(hipMemcpyAsync(B.uniforms.as<float>() + (size_t)slot * B.uni_cap, host_uniforms, (size_t)std::min(n_uniforms, 2 * sp->max_len) * 4, hipMemcpyHostToDevice, s));
+        Lm1Dyn* dslot = B.dyns.as<Lm1Dyn>() + slot; DecodeState* sslot = B.sts.as<DecodeState>() + slot;      // (plain values for the launch: a launch captures its arguments by value)
+        hipLaunchKernelGGL(lm1_slot_flag_kernel, dim3(1), dim3(64), 0, s, dslot, sslot, 1);
+        CV_HIP(hipStreamSynchronize(s));                        // the host copies above are stack / caller memory
+        S.open = 1; S.returned = 0; S.host = st; B.host_states[slot] = st; B.emb_table = emb_table; B.stream = s;
+    });
+}
+
+int cv_lm1_batch_decode(cv_lm1* m, int32_t n_steps, int32_t* out_tokens, int32_t* n_out, int32_t* finished, void* stream) {
+    return guarded([&] {
+        CV_CHECK(m && out_tokens && n_out && finished && n_steps > 0, "cv_lm1_batch_decode: bad arguments");
+        cv_lm1::Batch& B = m->batch;
+        CV_CHECK(B.nb > 0, "cv_lm1_batch_decode: cv_lm1_batch_begin first");
+        bool any = false;
+        for (int i = 0; i < B.nb; ++i) {
+            const cv_lm1::Slot& S = B.slots[i];
+            any = any || S.open;
+            CV_CHECK(!S.open || S.host.done || S.host.pos + n_steps <= S.cap, "cv_lm1_batch_decode: a slot's bound cache ends before these steps do");
+        }
+        CV_CHECK(any, "cv_lm1_batch_decode: no open slot (cv_lm1_batch_open first)");
+        hipStream_t s = resolve(m, stream);
+        B.stream = s;
+        for (int i = 0; i < n_steps; ++i) batch_step(m, s);
+        CV_HIP(hipMemcpyAsync(B.host_states.data(), B.sts.p, (size_t)B.nb * sizeof(DecodeState), hipMemcpyDeviceToHost, s));
+        CV_HIP(hipMemcpyAsync(B.host_tokens.data(), B.tokens.p, (size_t)B.nb * B.tok_cap * 4, hipMemcpyDeviceToHost, s));
+        CV_HIP(hipStreamSynchronize(s));
+        CV_HIP(hipGetLastError());
+        for (int i = 0; i < B.nb; ++i) {
+            cv_lm1::Slot& S = B.slots[i];
+            if (!S.open) { n_out[i] = 0; finished[i] = 1; continue; }
+            S.host = B.host_states[i];
+            const int after = std::min(S.host.n_tokens, B.tok_cap);
+            n_out[i] = std::max(0, std::min(after - S.returned, (int)n_steps));
+            for (int k = 0; k < n_out[i]; ++k) out_tokens[(size_t)i * n_steps + k] = B.host_tokens[(size_t)i * B.tok_cap + S.returned + k];
+            S.returned += n_out[i];
+            finished[i] = S.host.done ? 1 : 0;
+        }
+    });
+}
+
+int cv_lm1_batch_release(cv_lm1* m, int32_t slot) {
+    return guarded([&] {
+        CV_CHECK(m, "cv_lm1_batch_release: null handle");
+        cv_lm1::Batch& B = m->batch;
+        CV_CHECK(B.nb > 0, "cv_lm1_batch_release: cv_lm1_batch_begin first");
+        CV_CHECK(slot >= 0 && slot < B.nb, "cv_lm1_batch_release: slot out of range");
+        hipStream_t s = B.stream ? B.stream : resolve(m, nullptr);
+        Lm1Dyn* dslot = B.dyns.as<Lm1Dyn>() + slot; DecodeState* sslot = B.sts.as<DecodeState>() + slot;
+        hipLaunchKernelGGL(lm1_slot_flag_kernel, dim3(1), dim3(64), 0, s, dslot, sslot, 0);
+        CV_HIP(hipStreamSynchronize(s));                        // the caller may free the slot's cache rows when this returns
+        B.slots[slot] = cv_lm1::Slot{};
+    });
+}
+
+int cv_lm1_batch_logits(cv_lm1* m, int32_t slot, float* host_out, void* stream) {
+    return guarded([&] {
+        CV_CHECK(m && host_out, "cv_lm1_batch_logits: null argument");
+        CV_CHECK(m->batch.nb > 0, "cv_lm1_batch_logits: cv_lm1_batch_begin first");
+        CV_CHECK(slot >= 0 && slot < m->batch.nb, "cv_lm1_batch_logits: slot out of range");
+        CV_CHECK(m->batch.slots[slot].open, "cv_lm1_batch_logits: the slot holds no request");
+        hipStream_t s = resolve(m, stream);
+        CV_HIP(hipMemcpyAsync(host_out, m->batch.logits.as<float>() + (size_t)slot * m->n_out, (size_t)m->n_out * 4, hipMemcpyDeviceToHost, s));
+        CV_HIP(hipStreamSynchronize(s));
+    });
+}
+
 int64_t cv_lm1_stat(const cv_lm1* m, const char* name) {
     if (!m || !name) return -1;
     const std::string n(name);
     if (n == "steps") return m->steps;
     if (n == "graph_replays") return m->graph_replays;
+    if (n == "batch_steps") return m->batch_steps;
     if (n == "launches_per_step") return 3 + 5LL * m->n_layers;
     return -1;
 }

@@ -419,7 +419,28 @@ int cv_lm1_step(cv_lm1* m, const float* x_row, int32_t pos, float* logits, void*
 int cv_lm1_decode_begin(cv_lm1* m, const float* x_row, int32_t pos, const cv_sampling* sp, const float* emb_table, int32_t max_tokens, const float* host_uniforms,
                         int32_t n_uniforms, void* stream);
 int cv_lm1_decode(cv_lm1* m, int32_t n_steps, int32_t* out_tokens, int32_t* n_out, int32_t* finished, void* stream);
-int64_t cv_lm1_stat(const cv_lm1* m, const char* name);            /* "steps", "graph_replays", "launches_per_step"; -1 for an unknown name */
+/* Lock-step batched decode: up to 8 requests share ONE weight stream per generated token.  The reference has no counterpart - TransformerLM.inference
+ * (cosyvoice/llm/llm.py:162-223) is batch-1, concurrent requests each run that loop; what this stands in for is N such loops side by side (the role vLLM plays for the
+ * Qwen2 models, cli/model.py:281-290; here cv_llm_batch_*).  Every GEMV of the step reads a weight row once and applies it to every active slot's vector with the
+ * products and the summation order of the single-sequence kernel: a slot's logits, tokens and cache rows are bit-identical to cv_lm1_decode on that request alone,
+ * whatever the slot count and whichever slot it occupies.
+ *   cv_lm1_batch_begin   : sizes the per-slot state for nb slots (1..8) and marks all of them empty;
+ *   cv_lm1_batch_bind    : a slot's cache rows / tables (cv_lm1_bind's arguments); again whenever a buffer is reallocated - the slot's position and request are kept;
+ *   cv_lm1_batch_open    : cv_lm1_decode_begin for one slot (first input row, position, sampling parameters, token capacity >= sp->max_len); may be called between two
+ *                          decode calls to refill a released slot.  The slots of a batch share emb_table;
+ *   cv_lm1_batch_decode  : n_steps lock-step steps; per slot the tokens emitted by this call (out_tokens[slot * n_steps + k]), their count (n_out[slot]) and whether
+ *                          the slot has finished (finished[slot]; 1 for an empty slot).  A finished slot idles in the step (it rewrites its own row) until released;
+ *   cv_lm1_batch_release : frees a slot (its buffers may be freed afterwards); an empty slot reads and writes nothing;
+ *   cv_lm1_batch_logits  : test hook - one slot's logits after the last step (host [n_out]).
+ * The single-sequence entry points above are independent of the batch state of a handle. */
+int cv_lm1_batch_begin(cv_lm1* m, int32_t nb, void* stream);
+int cv_lm1_batch_bind(cv_lm1* m, int32_t slot, float* const* rows, const float* const* tabs, int32_t n_tab, int32_t cap, void* stream);
+int cv_lm1_batch_open(cv_lm1* m, int32_t slot, const float* x_row, int32_t pos, const cv_sampling* sp, const float* emb_table, int32_t max_tokens, const float* host_uniforms,
+                      int32_t n_uniforms, void* stream);
+int cv_lm1_batch_decode(cv_lm1* m, int32_t n_steps, int32_t* out_tokens, int32_t* n_out, int32_t* finished, void* stream);
+int cv_lm1_batch_release(cv_lm1* m, int32_t slot);
+int cv_lm1_batch_logits(cv_lm1* m, int32_t slot, float* host_out, void* stream);
+int64_t cv_lm1_stat(const cv_lm1* m, const char* name);            /* "steps", "graph_replays", "launches_per_step", "batch_steps"; -1 for an unknown name */
 int cv_lm1_set_option(cv_lm1* m, const char* name, int32_t value); /* "graph" (env CV_LM1_GRAPH): 1 replays the step as a hipGraph, 0 (default: measured 3 % faster per token) launches it kernel by kernel;
                                                                      * "gemv_rows" / "gemv_rows16" (1 | 2 | 4; env CV_LM1_ROWS / CV_LM1_ROWS16): output rows per 16-lane group of the decode GEMVs over
                                                                      * fp32 / bf16 matrices - the same bits, a different split of the rows over workgroups */
