@@ -17,6 +17,7 @@
 #include "api_common.h"
 #include "common.h"
 #include "llm_kernels.h"
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
@@ -731,6 +732,14 @@ void gemv(cv_lm1* m, int pro, const float* x, const float* g, const float* b, fl
 #undef LM1_GEMV
 }
 
+// The decode attention of one layer: nb == 0 is the single-sequence launch on dyn[0], nb >= 1 the batched one (blockIdx.z = slot, a slot's partials heads * LM1_SPLITS * 66
+// floats after the previous slot's).  Shared by step_body, batch_step and the kernel's test entry point (cv_lm1_attention).
+void launch_attn(const Lm1Dyn* dyn, int layer, int d, int heads, float scale, float* part, int nb, hipStream_t s) {
+    Lm1AttnArgs aa{dyn, layer, d, heads, scale, part};
+    if (nb > 0) { aa.slot_part = (long long)heads * LM1_SPLITS * 66; aa.batched = 1; }
+    hipLaunchKernelGGL(lm1_attn_kernel, dim3(heads, LM1_SPLITS, nb > 0 ? nb : 1), dim3(256), 0, s, aa);
+}
+
 // everything of a step after its first kernel
 void step_body(cv_lm1* m, float* logits, hipStream_t s) {
     const int d = m->d;
@@ -740,7 +749,7 @@ void step_body(cv_lm1* m, float* logits, hipStream_t s) {
         const Lm1Layer& L = m->L[i];
         const cv_lm1::L16 H = m->w16 ? m->L16s[i] : cv_lm1::L16{};
         gemv(m, LM1_PRO_LN, x0, L.ln1_g, L.ln1_b, 1e-12f, L.w_qkv, H.w_qkv, L.b_qkv, nullptr, nullptr, i, -1, 4 * d, d, ACT_NONE, s);
-        hipLaunchKernelGGL(lm1_attn_kernel, dim3(m->heads, LM1_SPLITS), dim3(256), 0, s, Lm1AttnArgs{m->dyn.as<Lm1Dyn>(), i, d, m->heads, 0.125f, part});
+        launch_attn(m->dyn.as<Lm1Dyn>(), i, d, m->heads, 0.125f, part, 0, s);
         gemv(m, LM1_PRO_MERGE, part, nullptr, nullptr, 0.f, L.w_out, H.w_out, L.b_out, x0, x1, -1, -1, d, d, ACT_NONE, s);
         gemv(m, LM1_PRO_LN, x1, L.ln2_g, L.ln2_b, 1e-12f, L.w1, H.w1, L.b1, nullptr, ff, -1, -1, m->ffn, d, m->act, s);
         gemv(m, LM1_PRO_NONE, ff, nullptr, nullptr, 0.f, L.w2, H.w2, L.b2, x1, x0, -1, -1, d, m->ffn, ACT_NONE, s);
@@ -804,9 +813,7 @@ void batch_step(cv_lm1* m, hipStream_t s) {
         const Lm1Layer& L = m->L[i];
         const cv_lm1::L16 H = m->w16 ? m->L16s[i] : cv_lm1::L16{};
         gemvb(m, LM1_PRO_LN, x0, d, L.ln1_g, L.ln1_b, 1e-12f, L.w_qkv, H.w_qkv, L.b_qkv, nullptr, 0, nullptr, 0, i, -1, 4 * d, d, ACT_NONE, s);
-        Lm1AttnArgs aa{dyns, i, d, m->heads, 0.125f, part};
-        aa.slot_part = sp; aa.batched = 1;
-        hipLaunchKernelGGL(lm1_attn_kernel, dim3(m->heads, LM1_SPLITS, nb), dim3(256), 0, s, aa);
+        launch_attn(dyns, i, d, m->heads, 0.125f, part, nb, s);
         gemvb(m, LM1_PRO_MERGE, part, sp, nullptr, nullptr, 0.f, L.w_out, H.w_out, L.b_out, x0, d, x1, d, -1, -1, d, d, ACT_NONE, s);
         gemvb(m, LM1_PRO_LN, x1, d, L.ln2_g, L.ln2_b, 1e-12f, L.w1, H.w1, L.b1, nullptr, 0, ff, m->ffn, -1, -1, m->ffn, d, m->act, s);
         gemvb(m, LM1_PRO_NONE, ff, m->ffn, nullptr, nullptr, 0.f, L.w2, H.w2, L.b2, x1, d, x0, d, -1, -1, d, m->ffn, ACT_NONE, s);
@@ -1139,6 +1146,86 @@ int cv_lm1_batch_logits(cv_lm1* m, int32_t slot, float* host_out, void* stream) 
         hipStream_t s = resolve(m, stream);
         CV_HIP(hipMemcpyAsync(host_out, m->batch.logits.as<float>() + (size_t)slot * m->n_out, (size_t)m->n_out * 4, hipMemcpyDeviceToHost, s));
         CV_HIP(hipStreamSynchronize(s));
+    });
+}
+
+// ---- test entry points of the decode kernels (tests/test_zzz_cosyvoice1_hip_kernels.py): the production launch helpers on caller-made operands -----------------------
+int cv_lm1_attention(int32_t nb, const float* const* rows, const float* const* tabs, const int32_t* n_tab, const int32_t* pos, int32_t d, int32_t heads, float scale, float* part,
+                     void* stream) {
+    return guarded([&] {
+        CV_CHECK(rows && tabs && n_tab && pos && part, "cv_lm1_attention: null argument");
+        CV_CHECK(nb >= 0 && nb <= LM1_MAX_SLOTS, "cv_lm1_attention: nb is 0 (the single-sequence launch) or 1..8 slots");
+        CV_CHECK(heads >= 1 && d == 64 * heads && d <= 1024, "cv_lm1_attention: 64-wide heads, model width up to 1024");
+        CV_CHECK(std::isfinite(scale) && scale > 0.f, "cv_lm1_attention: bad scale (finite and positive)");
+        CV_CHECK((reinterpret_cast<uintptr_t>(part) & 3) == 0, "cv_lm1_attention: unaligned part");
+        const int n = nb > 0 ? nb : 1;
+        std::vector<Lm1Dyn> h((size_t)n, Lm1Dyn{});
+        for (int i = 0; i < n; ++i) {
+            if (nb > 0 && pos[i] < 0) continue;                 // an inactive slot: flag clear, nothing of it is read
+            CV_CHECK(pos[i] >= 0 && pos[i] < LM1_SPLITS * LM1_MAX_KEYS_PER_SPLIT, "cv_lm1_attention: a position of up to 32767");
+            CV_CHECK(n_tab[i] >= pos[i] + 1, "cv_lm1_attention: the relative-position table must cover the keys (n_tab >= pos + 1)");
+            CV_CHECK(rows[i] && tabs[i] && aligned16(rows[i]) && aligned16(tabs[i]), "cv_lm1_attention: cache / table buffers of an active slot present and 16B aligned");
+            h[i].pos = pos[i]; h[i].n_tab = n_tab[i]; h[i].pad0 = 1;
+            h[i].rows[0] = const_cast<float*>(rows[i]); h[i].tabs[0] = tabs[i];
+        }
+        hipStream_t s = as_stream(stream);
+        DevBuf dyn;
+        dyn.ensure(h.size() * sizeof(Lm1Dyn));
+        CV_HIP(hipMemcpyAsync(dyn.p, h.data(), h.size() * sizeof(Lm1Dyn), hipMemcpyHostToDevice, s));
+        launch_attn(dyn.as<Lm1Dyn>(), 0, d, heads, scale, part, nb, s);
+        CV_HIP(hipStreamSynchronize(s));                        // the device block is this call's own
+        CV_HIP(hipGetLastError());
+    });
+}
+
+namespace {
+// what both GEMV hooks refuse (gemv() / gemvb() themselves check K); `who` is the hook's name
+void check_gemv_hook(const char* who, cv_lm1* m, int pro, const float* x, const float* g, const float* b, float eps, const float* W, const void* W16, const float* bias,
+                     const float* res, const float* y, int N, int K, int act) {
+    auto fail = [&](const char* what) { throw cv::Error(std::string(who) + ": " + what); };
+    if (!m) fail("null handle");
+    if (pro != LM1_PRO_NONE && pro != LM1_PRO_LN && pro != LM1_PRO_MERGE) fail("bad prologue (0 none, 1 LayerNorm, 2 merge)");
+    if (!x || !y || !aligned16(x) || (reinterpret_cast<uintptr_t>(y) & 3) != 0) fail("null / unaligned x or y");
+    if ((W == nullptr) == (W16 == nullptr)) fail("exactly one of W (fp32) and W16 (bf16)");
+    if (!aligned16(W) || !aligned16(W16)) fail("unaligned matrix");
+    if (W16 && !m->w16) fail("W16 needs a handle in bf16 mode (cv_lm1_use_bf16)");
+    if (N < 1 || K < 4 || K % 4 != 0 || K > LM1_MAX_K) fail("bad shape (N >= 1, K % 4 == 0, 4 <= K <= 4096)");
+    if (pro == LM1_PRO_LN && (K > 1024 || !g || !b || !aligned16(g) || !aligned16(b) || !(std::isfinite(eps) && eps >= 0.f)))
+        fail("the LayerNorm prologue takes K <= 1024, 16B-aligned gamma / beta and a finite eps >= 0");
+    if (pro == LM1_PRO_MERGE && (K % 64 != 0 || K > 1024)) fail("the merge prologue takes K = 64 heads <= 1024");
+    if (act != ACT_NONE && act != ACT_RELU && act != ACT_SILU) fail("bad activation (none, relu, silu)");
+    if ((reinterpret_cast<uintptr_t>(bias) & 3) != 0 || (reinterpret_cast<uintptr_t>(res) & 3) != 0) fail("unaligned bias / res");
+}
+}  // namespace
+
+int cv_lm1_gemv(cv_lm1* m, int32_t pro, const float* x, const float* g, const float* b, float eps, const float* W, const void* W16, const float* bias, const float* res, float* y,
+                int32_t N, int32_t K, int32_t act, void* stream) {
+    return guarded([&] {
+        check_gemv_hook("cv_lm1_gemv", m, pro, x, g, b, eps, W, W16, bias, res, y, N, K, act);
+        gemv(m, pro, x, g, b, eps, W, W16, bias, res, y, -1, -1, N, K, act, resolve(m, stream));
+    });
+}
+
+int cv_lm1_gemv_batch(cv_lm1* m, int32_t nb, uint32_t active_mask, int32_t pro, const float* x, int64_t sx, const float* g, const float* b, float eps, const float* W,
+                      const void* W16, const float* bias, const float* res, int64_t sres, float* y, int64_t sy, int32_t N, int32_t K, int32_t act, void* stream) {
+    return guarded([&] {
+        check_gemv_hook("cv_lm1_gemv_batch", m, pro, x, g, b, eps, W, W16, bias, res, y, N, K, act);
+        cv_lm1::Batch& B = m->batch;
+        CV_CHECK(nb >= 1 && nb <= LM1_MAX_SLOTS && B.nb == nb, "cv_lm1_gemv_batch: cv_lm1_batch_begin with these nb slots (1..8) first");
+        CV_CHECK((active_mask >> nb) == 0, "cv_lm1_gemv_batch: a mask bit beyond the slots");
+        CV_CHECK(sx >= 0 && sx % 4 == 0 && sres >= 0 && sy >= 0, "cv_lm1_gemv_batch: bad slot strides (sx a multiple of 4 floats, none negative)");
+        for (int i = 0; i < nb; ++i) CV_CHECK(!B.slots[i].open, "cv_lm1_gemv_batch: the handle has an open slot");
+        hipStream_t s = resolve(m, stream);
+        auto flags = [&](uint32_t mask) {
+            for (int i = 0; i < nb; ++i) {
+                Lm1Dyn* dslot = B.dyns.as<Lm1Dyn>() + i; DecodeState* sslot = B.sts.as<DecodeState>() + i;
+                hipLaunchKernelGGL(lm1_slot_flag_kernel, dim3(1), dim3(64), 0, s, dslot, sslot, (int)((mask >> i) & 1u));
+            }
+        };
+        flags(active_mask);
+        try { gemvb(m, pro, x, sx, g, b, eps, W, W16, bias, res, sres, y, sy, -1, -1, N, K, act, s); }
+        catch (...) { flags(0); throw; }
+        flags(0);
     });
 }
 

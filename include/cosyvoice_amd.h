@@ -440,6 +440,28 @@ int cv_lm1_batch_open(cv_lm1* m, int32_t slot, const float* x_row, int32_t pos, 
 int cv_lm1_batch_decode(cv_lm1* m, int32_t n_steps, int32_t* out_tokens, int32_t* n_out, int32_t* finished, void* stream);
 int cv_lm1_batch_release(cv_lm1* m, int32_t slot);
 int cv_lm1_batch_logits(cv_lm1* m, int32_t slot, float* host_out, void* stream);
+/* Test hooks (no reference counterpart): the decode step's kernels on caller-made operands, launched through the helpers the step itself launches through
+ * (tests/test_zzz_cosyvoice1_hip_kernels.py).  A refused call returns an error that names the hook and launches nothing.
+ *   cv_lm1_attention  : the one-query relative-position attention of one layer.  nb = 0: the single-sequence launch (grid heads x 8) on entry 0 of the arrays;
+ *                       nb = 1..8: the batched launch (grid heads x 8 x nb), pos[i] < 0 marks slot i inactive (its pointers may be null, its partials stay untouched).
+ *                       rows[i]: dev fp32 [pos[i] + 1][4 d] = (q + u | q + v | k | v) per position, the query is row pos[i]; tabs[i]: dev fp32 [2 n_tab[i] - 1][d], row m =
+ *                       relative position n_tab[i] - 1 - m (key j of n = pos + 1 sits at relative position n - 1 - j); part: dev fp32 [max(nb, 1)][heads][8][66] =
+ *                       (m, l, acc[64]) per key range, an empty range reports (-inf, 0).  The arrays rows / tabs / n_tab / pos are host memory.  Returns after the launch
+ *                       has finished.  Refused: a null or not 16-byte aligned pointer of an active slot, d != 64 heads or d > 1024, pos >= 32768, n_tab < pos + 1,
+ *                       nb outside 0..8, a scale that is not finite and positive.
+ *   cv_lm1_gemv       : y[N] = act(pro(x)[K] . W[N][kp]^T + bias) + res through the step's GEMV dispatcher (kp = K rounded up to 32; the columns K .. kp - 1 must be finite).
+ *                       pro 0: x is the vector; 1: LayerNorm(x; g, b, eps), K <= 1024; 2: x is attention partials [K / 64][8][66] merged into the vector, K <= 1024.
+ *                       Exactly one of W (fp32) and W16 (bf16; the handle must be in bf16 mode, cv_lm1_use_bf16); bias / res may be null; act: none, relu or silu.  The
+ *                       kernel form is the one the handle's gemv_wide / gemv16_wide / gemv_rows / gemv_rows16 options select for (N, K, dtype, pro), as in a step.
+ *   cv_lm1_gemv_batch : the same product for the nb slots of a handle after cv_lm1_batch_begin(nb) with no open slot: slot i (bit i of active_mask) reads x + i sx and
+ *                       res + i sres and writes y + i sy (strides in floats); of a slot whose bit is clear no pointer is read and nothing is written.  Every active slot has
+ *                       the bits of cv_lm1_gemv on its vector alone.  The slots' flags are clear again when the call returns. */
+int cv_lm1_attention(int32_t nb, const float* const* rows, const float* const* tabs, const int32_t* n_tab, const int32_t* pos, int32_t d, int32_t heads, float scale, float* part,
+                     void* stream);
+int cv_lm1_gemv(cv_lm1* m, int32_t pro, const float* x, const float* g, const float* b, float eps, const float* W, const void* W16, const float* bias, const float* res, float* y,
+                int32_t N, int32_t K, int32_t act, void* stream);
+int cv_lm1_gemv_batch(cv_lm1* m, int32_t nb, uint32_t active_mask, int32_t pro, const float* x, int64_t sx, const float* g, const float* b, float eps, const float* W,
+                      const void* W16, const float* bias, const float* res, int64_t sres, float* y, int64_t sy, int32_t N, int32_t K, int32_t act, void* stream);
 int64_t cv_lm1_stat(const cv_lm1* m, const char* name);            /* "steps", "graph_replays", "launches_per_step", "batch_steps"; -1 for an unknown name */
 int cv_lm1_set_option(cv_lm1* m, const char* name, int32_t value); /* "graph" (env CV_LM1_GRAPH): 1 replays the step as a hipGraph, 0 (default: measured 3 % faster per token) launches it kernel by kernel;
                                                                      * "gemv_rows" / "gemv_rows16" (1 | 2 | 4; env CV_LM1_ROWS / CV_LM1_ROWS16): output rows per 16-lane group of the decode GEMVs over
