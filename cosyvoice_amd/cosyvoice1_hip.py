@@ -932,17 +932,35 @@ class EstimatorHandle:
             pass
 
     def forward(self, x, mask, mu, t, spks, cond):
-        """ConditionalDecoder.forward (flow/decoder.py:204-291) in the reference's layouts: x, mu, cond [2, 80, T], mask [2, 1, T] (all ones), t [2], spks [2, 80] -> [2, 80, T]."""
+        """ConditionalDecoder.forward (flow/decoder.py:204-291) in the reference's layouts: x, mu, cond [2, 80, T], mask [2, 1, T], t [2], spks [2, 80] -> [2, 80, T].
+        mask: all ones, or a PREFIX mask per row (ones for a row's valid frames, then zeros: a padded batch).  A padded row's valid frames come out as for that row
+        alone at its own length, its padded frames as zeros (cv_flow_estimator_masked) - NOT as the reference's padded form, whose GroupNorm averages over the padding."""
         T = x.shape[2]
-        assert bool((mask == 1).all()), "batch-1 requests: the mask is all ones"
+        m2 = mask.reshape(2, T).to("cpu", F32)
+        lens = m2.sum(dim=1).to(torch.int64)
+        if not torch.equal(m2, (torch.arange(T).unsqueeze(0) < lens.unsqueeze(1)).to(F32)) or int(lens.min()) < 1:
+            raise NotImplementedError("the estimator computes its masks from lengths: a mask row must be ones for its valid frames followed by zeros, at least one valid frame")
         args = [self.lib.hook(a.to(self.dev, F32).contiguous()) for a in (x, mask, mu, t, spks, cond)]
         out = self.lib.hook(torch.empty(2, self.mel, T, dtype=F32, device=self.dev))
-        self.lib.cv_flow_estimator(self._h, *[_p(a) for a in args], C.c_int32(T), C.c_int32(0), _p(out), stream_ptr(self.lib))
+        if int(lens.min()) == T:
+            self.lib.cv_flow_estimator(self._h, *[_p(a) for a in args], C.c_int32(T), C.c_int32(0), _p(out), stream_ptr(self.lib))
+        else:
+            kl = (C.c_int32 * 2)(int(lens[0]), int(lens[1]))
+            self.lib.cv_flow_estimator_masked(self._h, _p(args[0]), _p(args[1]), kl, *[_p(a) for a in args[2:]], C.c_int32(T), C.c_int32(0), _p(out), stream_ptr(self.lib))
         return out
 
     def solve(self, x, mu, spk, cond, T, n_steps):
         """x [T, 80] channel-last (in: z, out: the mel after n_steps Euler steps), mu / cond [T, 80], spk [1, 80]: ConditionalCFM.solve_euler (flow_matching.py:71-124)."""
         self.lib.cv_flow_solve(self._h, _p(x), _p(mu), _p(spk), _p(cond), C.c_int32(T), C.c_int32(n_steps), stream_ptr(self.lib))
+        return x
+
+    def solve_batch(self, x, mu, spk, cond, lens, n_steps):
+        """`solve` for n (1..8) requests of different lengths in ONE padded pass (cv_flow_solve_ragged): x / mu / cond [n, Tmax, 80] channel-last and zero behind lens[i],
+        spk [n, 80], lens a list of ints (1..Tmax).  x[i, :lens[i]] comes out bit-identical to `solve` on request i alone; the frames behind stay zero."""
+        n, Tmax = int(x.shape[0]), int(x.shape[1])
+        assert len(lens) == n and mu.shape == x.shape == cond.shape and tuple(spk.shape) == (n, self.mel) and all(a.is_contiguous() for a in (x, mu, spk, cond))
+        self.lib.cv_flow_solve_ragged(self._h, C.c_int32(n), _p(x), _p(mu), _p(spk), _p(cond), (C.c_int32 * n)(*[int(v) for v in lens]), C.c_int32(Tmax),
+                                      C.c_int32(n_steps), stream_ptr(self.lib))
         return x
 
 
@@ -984,7 +1002,50 @@ class MaskedDiffWithXvec(C1.MaskedDiffWithXvec):
         with self.lock:                                          # concurrent requests of one CosyVoiceModel share this stage object
             return self._inference(token, prompt_token, prompt_feat, embedding, flow_cache)
 
+    @torch.inference_mode()
+    def inference_batch(self, items):
+        """`inference` for several OFFLINE requests (items: dicts of `inference`'s arguments, flow_cache empty or absent) whose Euler solves share one padded pass
+        (EstimatorHandle.solve_batch; the reference has no batched form of this model).  Encoder, length regulator and speaker projection run per request as in
+        `inference`; mu, cond and the noise are padded to the longest request.  Returns the list of [1, 80, mel_len2]: each bit-identical to `inference` on that
+        request alone.  The noise is drawn once per request in list order (`_draw_noise`)."""
+        if not isinstance(self.estimator, EstimatorHandle):
+            raise NotImplementedError("inference_batch needs the \"handle\" estimator (the \"operators\" estimator is batch-1)")
+        if not 1 <= len(items) <= 8:
+            raise ValueError("inference_batch: 1..8 requests per pass")
+        for it in items:
+            cache = it.get("flow_cache")
+            if cache is not None and cache.shape[2] != 0:
+                raise ValueError("inference_batch is offline: a request with a non-empty flow cache (a streaming chunk) goes through `inference`")
+        with self.lock:
+            K, mel = self.k, self.output_size
+            fronts = [self._front(it["token"], it["prompt_token"], it["prompt_feat"], it["embedding"]) for it in items]
+            lens = [f[3] for f in fronts]
+            n, Tmax = len(items), max(lens)
+            x, mu, cond, spk = K.zeros(n, Tmax, mel), K.zeros(n, Tmax, mel), K.zeros(n, Tmax, mel), K.new(n, mel)
+            for i, (mu_i, spk_i, cond_i, T, _, _) in enumerate(fronts):
+                x[i, :T].copy_(self._draw_noise(T)[0].t().to(K.dev))
+                mu[i, :T].copy_(mu_i)
+                cond[i, :T].copy_(cond_i)
+                spk[i].copy_(spk_i[0])
+            self.estimator.solve_batch(x, mu, spk, cond, lens, self.n_timesteps)
+            outs = []
+            for i, (_, _, _, T, mel_len1, mel_len2) in enumerate(fronts):
+                out = K.new(mel, mel_len2)
+                K.lib.cv_transpose(_p(x[i, mel_len1:T]), _p(out), C.c_int32(mel_len2), C.c_int32(mel), stream_ptr(K.lib))
+                outs.append(out.unsqueeze(0))
+            return outs
+
     def _inference(self, token, prompt_token, prompt_feat, embedding, flow_cache):
+        K, mel = self.k, self.output_size
+        mu, spk, cond, T, mel_len1, mel_len2 = self._front(token, prompt_token, prompt_feat, embedding)
+        feat, flow_cache = self._cfm(mu, spk, cond, T, mel_len1, flow_cache)
+        out = K.new(mel, mel_len2)                                                             # [T][80] rows mel_len1.. -> the reference's [1, 80, mel_len2]
+        K.lib.cv_transpose(_p(feat[mel_len1:]), _p(out), C.c_int32(mel_len2), C.c_int32(mel), stream_ptr(K.lib))
+        return out.unsqueeze(0), flow_cache
+
+    def _front(self, token, prompt_token, prompt_feat, embedding):
+        """Everything of `inference` in front of the CFM: speaker projection, encoder, length regulator, the prompt condition -> (mu [T, 80], spk [1, 80], cond [T, 80],
+        T, mel_len1, mel_len2)."""
         assert token.shape[0] == 1
         K, mel = self.k, self.output_size
         e = torch.nn.functional.normalize(embedding.float().cpu(), dim=1)
@@ -1009,15 +1070,16 @@ class MaskedDiffWithXvec(C1.MaskedDiffWithXvec):
         cond = K.zeros(T, mel)
         if mel_len1:
             cond[:mel_len1].copy_(prompt_feat.reshape(mel_len1, mel).to(K.dev, F32))
-        feat, flow_cache = self._cfm(mu, spk, cond, T, mel_len1, flow_cache)
-        out = K.new(mel, mel_len2)                                                             # [T][80] rows mel_len1.. -> the reference's [1, 80, mel_len2]
-        K.lib.cv_transpose(_p(feat[mel_len1:]), _p(out), C.c_int32(mel_len2), C.c_int32(mel), stream_ptr(K.lib))
-        return out.unsqueeze(0), flow_cache
+        return mu, spk, cond, T, mel_len1, mel_len2
+
+    def _draw_noise(self, T):
+        """The initial noise of one request, [1, 80, T]: drawn on the host like the reference's `.to(mu.device)` - the same stream on every device.  One call per request."""
+        return torch.randn(1, self.output_size, T)
 
     def _cfm(self, mu, spk, cond, T, prompt_len, cache):
         """ConditionalCFM.forward + solve_euler (flow/flow_matching.py:36-124) with the prompt / overlap flow cache of CosyVoice-300M."""
         K, mel = self.k, self.output_size
-        z = torch.randn(1, mel, T)                               # drawn on the host like the reference's `.to(mu.device)`: same stream on every device
+        z = self._draw_noise(T)
         cache = torch.zeros(1, mel, 0, 2) if cache is None else cache.cpu()
         n_cache = cache.shape[2]
         if n_cache != 0:
@@ -1118,12 +1180,20 @@ class CosyVoiceModel(C1.CosyVoiceModel):
         self.flow = MaskedDiffWithXvec(ld(flow_model), lib=lib, precision="bf16" if fp16 else "fp32", **{k: kw[k] for k in ("enc_heads", "est_heads", "input_frame_rate") if k in kw})
         self.hift = HiFTGenerator({k.replace("generator.", ""): v for k, v in ld(hift_model).items()}, hift_cfg or cv1()[1], lib=lib, **kw.get("hift", {}))
 
-    def tts_batch(self, requests, slots=8, speed=1.0):
+    def tts_batch(self, requests, slots=8, speed=1.0, flow_batch=1, flow_pad=1.25):
         """Offline synthesis of several requests whose speech tokens come from ONE batched decode loop (TransformerLM.inference_batch: one weight stream per token for
         all of them; the reference runs one `tts` - cli/model.py:175-242 - per request).  requests: a list of dicts of `tts`'s keyword arguments (text, llm_embedding,
-        flow_embedding, prompt_text, llm_prompt_speech_token, flow_prompt_speech_token, prompt_speech_feat).  Each request that finishes goes through the offline
-        `token2wav` path on its own (the U-Net flow is batch-1); yields (index, {'tts_speech': [1, S] fp32 cpu}) in the order the requests finish."""
+        flow_embedding, prompt_text, llm_prompt_speech_token, flow_prompt_speech_token, prompt_speech_feat).  flow_batch = 1 (the default): each request that finishes
+        goes through the offline `token2wav` path on its own; yields (index, {'tts_speech': [1, S] fp32 cpu}) in the order the requests finish.
+        flow_batch > 1: finished requests wait for each other and share a padded flow pass (MaskedDiffWithXvec.inference_batch; every mel bit-identical to the request
+        alone).  The waiting requests are flushed when there are flow_batch of them, when nothing is decoding any more, or when the requests still decoding could not
+        fill the group; a flush is cut into passes by the rule of CosyVoice2Model._flow_groups (longest first, members within 1 / flow_pad of the longest - flow_pad
+        defaults to that model's 1.25).  The vocoder runs per request; a pass's requests are yielded together, longest first.  Measured on the MI355X at full size
+        (profiles/cv1_flow_batch.txt): one padded pass against N single passes is 1.6 / 2.1 / 2.5 x faster at N = 2 / 4 / 8 in fp32 and 1.9 / 3.4 / 5.5 x in bf16 mode -
+        recommended (4 .. 8) wherever throughput matters more than the latency of the first finished request, which now waits for its partners."""
+        import types
         import uuid as uuid_mod
+        from .model import CosyVoice2Model
         e0, t = torch.zeros(1, 0, dtype=torch.int32), (lambda n: torch.tensor([n], dtype=torch.int32))
         get = lambda r, k, d: r[k] if k in r else d
         lm_reqs = []
@@ -1141,6 +1211,25 @@ class CosyVoiceModel(C1.CosyVoiceModel):
                 self.flow_cache_dict[u] = torch.zeros(1, 80, 0, 2)
         gen = self.llm.inference_batch(lm_reqs, slots=slots, mark_end=True)
         silent = [0] * len(requests)
+        waiting, decoding = [], len(requests)                        # flow_batch > 1: (index, {flow_prompt_speech_token}, tokens) of finished requests; requests not finished
+        rule = types.SimpleNamespace(flow_batch=flow_batch, flow_pad=flow_pad)
+
+        def flush():
+            for group in CosyVoice2Model._flow_groups(rule, waiting):
+                if len(group) == 1:
+                    j, r = group[0][0], requests[group[0][0]]
+                    allt = torch.tensor(group[0][2], dtype=torch.int64).reshape(1, -1)
+                    yield j, {"tts_speech": self.token2wav(token=allt, prompt_token=get(r, "flow_prompt_speech_token", e0), prompt_feat=get(r, "prompt_speech_feat", torch.zeros(1, 0, 80)),
+                                                           embedding=get(r, "flow_embedding", torch.zeros(0, 192)), uuid=uuids[j], finalize=True, speed=speed).cpu()}
+                    continue
+                mels = self.flow.inference_batch([dict(token=torch.tensor(toks, dtype=torch.int32).reshape(1, -1), prompt_token=get(requests[j], "flow_prompt_speech_token", e0),
+                                                       prompt_feat=get(requests[j], "prompt_speech_feat", torch.zeros(1, 0, 80)),
+                                                       embedding=get(requests[j], "flow_embedding", torch.zeros(0, 192))) for j, _, toks in group])
+                for (j, _, _), mel in zip(group, mels):              # the finalize branch of token2wav (cli/model.py:164-172) without caches: an offline request has none
+                    if speed != 1.0:
+                        mel = torch.nn.functional.interpolate(mel, size=int(mel.shape[2] / speed), mode="linear")
+                    yield j, {"tts_speech": self.hift.inference(speech_feat=mel, cache_source=torch.zeros(1, 1, 0))[0].cpu()}
+            waiting.clear()
         try:
             for i, toks in gen:
                 u = uuids[i]
@@ -1156,6 +1245,12 @@ class CosyVoiceModel(C1.CosyVoiceModel):
                     continue
                 self.llm_end_dict[u] = True
                 r = requests[i]
+                decoding -= 1
+                if flow_batch > 1:
+                    waiting.append((i, dict(flow_prompt_speech_token=get(r, "flow_prompt_speech_token", e0)), list(self.tts_speech_token_dict[u])))
+                    if len(waiting) >= flow_batch or decoding == 0 or len(waiting) + decoding < flow_batch:
+                        yield from flush()
+                    continue
                 allt = torch.tensor(self.tts_speech_token_dict[u], dtype=torch.int64).reshape(1, -1)
                 wav = self.token2wav(token=allt, prompt_token=get(r, "flow_prompt_speech_token", e0), prompt_feat=get(r, "prompt_speech_feat", torch.zeros(1, 0, 80)),
                                      embedding=get(r, "flow_embedding", torch.zeros(0, 192)), uuid=u, finalize=True, speed=speed).cpu()

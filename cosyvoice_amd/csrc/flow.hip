@@ -120,6 +120,8 @@ struct cv_flow {
     int enc_cap = 0, est_cap = 0, est_nz = 0, t_cap = 0, inf_cap = 0; long long inf_rows = 0;
     // padded batches (cv_flow_inference_ragged): key counts per estimator batch row, fixed device address (captured graphs read the current content)
     DevBuf klen; std::vector<int> host_klen; const int* cur_klen = nullptr;
+    // padded passes of the CosyVoice-300M U-Net (cfg.estimator == 2): valid frames per estimator batch row AND resolution level, [levels][nz] (unet1_len_table)
+    DevBuf ulen; std::vector<int> host_ulen; const int* cur_ulen = nullptr;
     // hipGraph cache of the whole Euler solve, keyed by (T, n_steps, streaming): ~5000 launches per utterance become one replay.
     // A key is captured the second time it is seen (streaming requests change T every chunk and would only pay the instantiation).
     int use_graph = 1;
@@ -886,13 +888,28 @@ static void estimator_forward(cv_flow* m, int T, int t_row, int t_rows_total, bo
 // The same stage as above with three differences: the convolutions are centred (pad 1 on both sides), a Block1D normalises with GroupNorm(8) over (channels of the
 // group x TIME) instead of a LayerNorm per frame, and the stream changes resolution (stride-2 convolution down, transposed convolution up, cut to the skip's length).
 // The transformer blocks are the ones of the causal U-Net: stage_blocks() with full attention - in bf16 mode the fused kernels of flow_fused.h / flow_big.h / flow_band.h.
-// Batch-1 requests: the mask is all ones.
-static void unet1_forward(cv_flow* m, int T, int t_row, int t_rows_total, bool t_shared, hipStream_t s, int nz = 2) {
+// Batch-1 requests: the mask is all ones and `len` is null.
+//
+// Padded passes (`len`: device int32 [levels][nz], row k = the valid frames of every batch row at resolution level k, unet1_len_table): this estimator is NOT causal -
+// the centred convolutions, the stride-2 / transposed convolutions and GroupNorm's statistics over time all let the frames behind a row's end into its valid frames.
+// What keeps them out: GroupNorm takes its statistics over a row's own frames and writes zeros behind them (group_norm_len), attention takes the level's lengths as key
+// counts, and wherever the reference has `x * mask` without a GroupNorm after it the padded rows are zeroed (zero_tail_rows): the packed input, a stage's output after its
+// transformer blocks, and what the resampling convolutions write behind a row's new end.  A valid row then reads exactly what it reads behind the end of the row alone
+// (zeros), through the same kernels: its bits are those of the row alone at its own length.  The reference's padded form (flow/decoder.py:210-291) masks the same places
+// but normalises over the padded length - it does not reproduce its own batch-1 result, and is deliberately not what is built here.
+static void unet1_forward(cv_flow* m, int T, int t_row, int t_rows_total, bool t_shared, hipStream_t s, int nz = 2, const int* len = nullptr) {
     const auto& c = m->cfg; const int C = c.est_ch, G = 8;
     float* pp[2] = {m->s_a.as<float>(), m->s_c.as<float>()};
     float* xb = m->s_b.as<float>(); float* cat = m->s_cat.as<float>(); double* gn = m->u_gn.as<double>();
     const bool fused = m->bf16_mfma && m->fused && C <= 256 && m->wbf16;
     auto conv = [&](const Lin& l, const float* in, int Tn, float* out, const float* res) { conv_cl(l, in, Tn, Tn, nz, l.taps / 2, 1, out, ACT_NONE, 0.f, res, s); };
+    int rl = 0;                              // resolution level of the stream: + 1 behind a Downsample1D, - 1 behind an Upsample1D
+    auto gnorm = [&](const float* in, float* out, int Tn, const LN& ln, const float* col_add, long long col_add_batch) {
+        if (len) group_norm_len(in, out, nz, Tn, C, G, len + rl * nz, ln.g, ln.b, 1e-5f, ACT_MISH, col_add, col_add_batch, gn, s);
+        else group_norm(in, out, nz, Tn, C, G, ln.g, ln.b, 1e-5f, ACT_MISH, col_add, col_add_batch, gn, s);
+    };
+    auto ztail = [&](float* p, int Tn, int Cn) { if (len) zero_tail_rows(p, nz, Tn, Cn, len + rl * nz, s); };
+    ztail(m->s_in.as<float>(), T, 4 * c.mel);                        // (the broadcast speaker vector is not zero behind a row's end)
     const float* cur = m->s_in.as<float>();
     int Tc = T, flip = 0, level = 0;
     std::vector<int> skip_t;
@@ -909,11 +926,12 @@ static void unet1_forward(cv_flow* m, int T, int t_row, int t_rows_total, bool t
         float* x = pp[flip];                 // stage output (cur never aliases it)
         // ResnetBlock1D (matcha decoder.py): block1 -> + mlp(t) -> block2 -> + res_conv(x)
         conv(st.res.conv1, cur, Tc, x, nullptr);
-        group_norm(x, xb, nz, Tc, C, G, st.res.ln1.g, st.res.ln1.b, 1e-5f, ACT_MISH, tm, t_shared ? 0 : C, gn, s);
+        gnorm(x, xb, Tc, st.res.ln1, tm, t_shared ? 0 : C);
         conv(st.res.conv2, xb, Tc, x, nullptr);
-        group_norm(x, xb, nz, Tc, C, G, st.res.ln2.g, st.res.ln2.b, 1e-5f, ACT_MISH, nullptr, 0, gn, s);
+        gnorm(x, xb, Tc, st.res.ln2, nullptr, 0);
         conv(st.res.res, cur, Tc, x, xb);
-        stage_blocks(m, st, x, Tc, nz, 0, 0, 0, nullptr, fused, s);
+        stage_blocks(m, st, x, Tc, nz, 0, 0, 0, len ? len + rl * nz : nullptr, fused, s);
+        ztail(x, Tc, C);                     // before the skip copy and whatever convolution follows
         flip ^= 1;
         if (u.kind == 0) { CV_HIP(hipMemcpyAsync(m->u_skip[level].p, x, (size_t)R * C * 4, hipMemcpyDeviceToDevice, s)); skip_t.push_back(Tc); ++level; }
         if (u.post == 0) { cur = x; continue; }
@@ -926,29 +944,46 @@ static void unet1_forward(cv_flow* m, int T, int t_row, int t_rows_total, bool t
             a.C = y; a.N = l.N; a.act = ACT_NONE; a.out_scale = 1.f; a.a_bf16 = m->bf16_mfma && l.bf16;
             int Tn;
             if (u.post == 2) {               // Downsample1D: output row j = rows 2 j - 1 .. 2 j + 1, contiguous in a channel-last sequence
-                Tn = (Tc - 1) / 2 + 1;
+                Tn = (Tc - 1) / 2 + 1; ++rl; // (padded pass, odd length: the last valid output reads the first padded row - zeroed above)
                 a.lda = 2 * C; a.a_off0 = -C; a.tap_step = 0; a.M = Tn; a.ldc = l.N; a.c_batch = (long long)Tn * l.N; a.c_len = a.c_batch;
             } else {                         // Upsample1D: GEMM row j = output rows 2 j - 1, 2 j (phase r of the kernel in columns r C .. r C + C), tap q reads row j - q
-                Tn = 2 * Tc;
+                Tn = 2 * Tc; --rl;           // (padded pass: GEMM row len reads rows len and len - 1 - the first of them zeroed above)
                 a.lda = C; a.a_off0 = 0; a.tap_step = -C; a.M = Tc + 1; a.ldc = l.N; a.c_off = -C; a.c_batch = (long long)Tn * C; a.c_len = a.c_batch;
             }
             a.res_batch = a.c_batch; a.row_scale_batch = a.M;
             gemm_conv(a, l.bf16, nz, s);
             Tc = Tn;
         }
+        ztail(y, Tc, C);                     // a convolution writes its bias (and its window's reach) behind the row's end: the next one must read zeros there
         cur = y; flip ^= 1;
     }
-    CV_CHECK(Tc == T && skip_t.empty(), "flow(unet1): the up path must come back to the input length");
+    CV_CHECK(Tc == T && skip_t.empty() && rl == 0, "flow(unet1): the up path must come back to the input length");
     float* y = pp[flip];
     conv(m->final_conv, cur, T, y, nullptr);
-    group_norm(y, xb, nz, T, C, G, m->final_ln.g, m->final_ln.b, 1e-5f, ACT_MISH, nullptr, 0, gn, s);
+    gnorm(y, xb, T, m->final_ln, nullptr, 0);
     conv(m->final_proj, xb, T, m->s_out.as<float>(), nullptr);
+    ztail(m->s_out.as<float>(), T, c.mel);                           // `output * mask`: the Euler update then leaves the padded frames of x at zero
+}
+// The level-length table of a padded pass: len0 [nz] (host, each 1..T) -> [levels][nz] on the device, level k + 1 = (len_k - 1) / 2 + 1 (the reference's mask[:, :, ::2]);
+// >= 1 at every level, so no attention row ever has zero keys.
+static const int* unet1_len_table(cv_flow* m, const int* len0, int nz, hipStream_t s) {
+    int levels = 1;
+    for (const auto& u : m->ust) levels += u.post == 2;
+    CV_CHECK(nz >= 1 && nz <= 16 && levels <= 8, "flow(unet1): at most 16 estimator rows and 8 resolution levels in a padded pass");
+    m->ulen.ensure((size_t)8 * 16 * sizeof(int));
+    m->host_ulen.assign((size_t)levels * nz, 0);
+    for (int z = 0; z < nz; ++z) {
+        int l = len0[z];
+        for (int k = 0; k < levels; ++k) { m->host_ulen[(size_t)k * nz + z] = l; l = (l - 1) / 2 + 1; }
+    }
+    CV_HIP(hipMemcpyAsync(m->ulen.p, m->host_ulen.data(), m->host_ulen.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    return m->ulen.as<int>();
 }
 
 // One estimator evaluation over nz batch rows: with est_streams = 2 (and an even nz) the two halves of the batch rows run as independent launch chains
 // on `s` and on the handle's side stream, forked and joined through events (graph edges when `s` is being captured).
 static void estimator_eval(cv_flow* m, int T, int t_row, int t_rows_total, bool t_shared, int streaming, hipStream_t s, int nz = 2) {
-    if (m->cfg.estimator == 2) { unet1_forward(m, T, t_row, t_rows_total, t_shared, s, nz); return; }
+    if (m->cfg.estimator == 2) { unet1_forward(m, T, t_row, t_rows_total, t_shared, s, nz, m->cur_ulen); return; }
     if ((m->est_streams < 2 && !m->two_chains_now) || nz < 2 || (nz & 1)) { estimator_forward(m, T, t_row, t_rows_total, t_shared, streaming, s, nz, 0); return; }
     if (!m->side_stream) {
         CV_HIP(hipStreamCreateWithFlags(&m->side_stream, hipStreamNonBlocking));
@@ -1125,11 +1160,12 @@ static void solve_euler(cv_flow* m, float* x /*[nu][T][mel] in/out*/, const floa
             hipLaunchKernelGGL(cfg_euler_kernel, dim3(nblk(n)), dim3(256), 0, s, x, m->s_out.as<float>(), n, dts[st], c.cfg_rate);
         }
     };
-    const auto key = std::make_tuple(T, n_steps, (streaming ? 1 : 0) + 2 * nu + (m->cur_klen ? 64 : 0));     // a padded batch bakes the klen pointer into its launches
+    const auto key = std::make_tuple(T, n_steps, (streaming ? 1 : 0) + 2 * nu + (m->cur_klen ? 64 : 0) + (m->cur_ulen ? 128 : 0));     // a padded batch bakes the klen pointer (U-Net of CosyVoice-300M: the level-length table and its other launches) into its launches
     // Graphs pay where the launches are short next to the host's ~4 us per launch (one utterance: 3640 launches of ~10 us).  A shared pass over several
     // utterances is GPU-bound launch by launch - the host stays ahead - while capturing and instantiating its ~5000 nodes costs tens of milliseconds per new
     // shape, and offline batches bring a new Tmax with almost every group: passes of at least graph_max_rows estimator rows run eager.
-    const bool graphable = m->use_graph && (m->graph_max_rows <= 0 || 2LL * nu * T < m->graph_max_rows);
+    // (a padded pass of the CosyVoice-300M U-Net runs eager: a new Tmax with almost every group, and that handle's use_graph default is off anyway)
+    const bool graphable = m->use_graph && !m->cur_ulen && (m->graph_max_rows <= 0 || 2LL * nu * T < m->graph_max_rows);
     auto it = m->graphs.find(key);
     if (graphable && it != m->graphs.end() && x == m->f_x.as<float>()) {
         m->graph_used[key] = ++m->graph_clock;
@@ -1234,6 +1270,9 @@ static void flow_estimator_call(cv_flow* m, const float* x, const float* mask, c
     if (dit) { dit_reserve(m, T); dit_time_reserve(m, 2); } else { est_reserve(m, T); time_reserve(m, 2); }
     if (key_len) {                         // padded mask: the rows' key counts, read by the attention kernels (AttnArgs::klen) - what a padded pass of several utterances uses
         CV_CHECK(mask && key_len[0] >= 1 && key_len[0] <= T && key_len[1] >= 1 && key_len[1] <= T, "cv_flow_estimator_masked: key_len must be 1..T and needs the mask");
+    }
+    if (key_len && c.estimator == 2) m->cur_ulen = unet1_len_table(m, key_len, 2, s);       // the U-Net of CosyVoice-300M: lengths per resolution level (unet1_forward)
+    else if (key_len) {
         m->klen.ensure(64 * sizeof(int));
         m->host_klen.assign(key_len, key_len + 2);
         CV_HIP(hipMemcpyAsync(m->klen.p, m->host_klen.data(), 2 * sizeof(int), hipMemcpyHostToDevice, s));
@@ -1244,8 +1283,8 @@ static void flow_estimator_call(cv_flow* m, const float* x, const float* mask, c
         if (dit) dit_time_embed(m, 2, s); else time_embed(m, 2, s);
         hipLaunchKernelGGL(pack_est_input_kernel, dim3(nblk(2LL * T * 4 * c.mel)), dim3(256), 0, s, x, mu, spks, cond, m->s_in.as<float>(), T, c.mel, 0, 1);
         if (dit) dit_forward(m, T, 0, 2, false, streaming, s); else estimator_eval(m, T, 0, 2, false, streaming, s);
-    } catch (...) { m->cur_klen = nullptr; throw; }
-    m->cur_klen = nullptr;
+    } catch (...) { m->cur_klen = nullptr; m->cur_ulen = nullptr; throw; }
+    m->cur_klen = nullptr; m->cur_ulen = nullptr;
     // without key_len `mask` must be all ones for the in-kernel (index-computed) attention masks to be exact; either way it is applied to the output
     hipLaunchKernelGGL(to_channel_first_kernel, dim3(nblk(2LL * T * c.mel)), dim3(256), 0, s, m->s_out.as<float>(), out, 2, T, c.mel, 0, mask);
 }
@@ -1318,6 +1357,8 @@ int cv_flow_estimator_masked(cv_flow* m, const float* x, const float* mask, cons
 // embedding [nu][spk_dim], mel_out [nu][mel][T - mel_len1].  nu = 1 is cv_flow_inference.
 static void flow_inference(cv_flow* m, int nu, const int32_t* token_ids, int n_tok, const float* prompt_feat, int mel_len1, const float* embedding,
                            const float* noise_cl, int streaming, int finalize, int n_timesteps, float* mel_out, int32_t* mel_len2_out, void* stream) {
+    CV_CHECK(m->cfg.estimator != 2, "cv_flow_inference / cv_flow_inference_batch: a CosyVoice-300M U-Net handle (estimator == 2) holds no encoder - its entry points are "
+                                    "cv_flow_estimator, cv_flow_estimator_masked, cv_flow_solve and cv_flow_solve_ragged");
     FlowScope scope(m);
     const auto& c = m->cfg; const int d = c.dim;
     hipStream_t s = resolve(m, stream);
@@ -1375,6 +1416,7 @@ static void flow_inference(cv_flow* m, int nu, const int32_t* token_ids, int n_t
 // utterance alone.  The valid rows are therefore bit-identical to the single pass; the padded rows compute finite values nobody reads.
 static void flow_inference_ragged(cv_flow* m, int nu, const int32_t* token_ids, const int32_t* n_tok, const float* prompt_feat, const int32_t* mel_len1, const float* embedding,
                                   const float* noise_cl, int streaming, int finalize, int n_timesteps, float* mel_out, int32_t* mel_len2_out, void* stream) {
+    CV_CHECK(m->cfg.estimator != 2, "cv_flow_inference_ragged: a CosyVoice-300M U-Net handle (estimator == 2) holds no encoder - its padded pass is cv_flow_solve_ragged");
     FlowScope scope(m);
     const auto& c = m->cfg; const int d = c.dim;
     hipStream_t s = resolve(m, stream);
@@ -1451,6 +1493,27 @@ int cv_flow_solve(cv_flow* m, float* x, const float* mu, const float* spks, cons
         CV_HIP(hipMemcpyAsync(m->f_cond.p, cond, per, hipMemcpyDeviceToDevice, s)); CV_HIP(hipMemcpyAsync(m->f_spk.p, spks, (size_t)c.mel * 4, hipMemcpyDeviceToDevice, s));
         solve_euler(m, m->f_x.as<float>(), m->f_mu.as<float>(), m->f_spk.as<float>(), m->f_cond.as<float>(), T, n_timesteps, 0, s, 1);
         CV_HIP(hipMemcpyAsync(x, m->f_x.p, per, hipMemcpyDeviceToDevice, s));
+    });
+}
+// n_utt utterances of DIFFERENT lengths through one Euler solve of the CosyVoice-300M U-Net: the estimator sees 2 n_utt rows of Tmax frames, row z = (conditioned |
+// unconditioned) * n_utt + utterance, with the level-length table of unet1_forward.  The solve runs on the caller's buffers (a padded pass is never captured).
+int cv_flow_solve_ragged(cv_flow* m, int32_t n_utt, float* x, const float* mu, const float* spks, const float* cond, const int32_t* len, int32_t Tmax, int32_t n_timesteps,
+                         void* stream) {
+    return guarded([&] {
+        CV_CHECK(m && x && mu && spks && cond && len, "cv_flow_solve_ragged: null argument");
+        CV_CHECK(m->finalized && m->cfg.estimator == 2, "cv_flow_solve_ragged: needs a finalized handle of the CosyVoice-300M U-Net (estimator == 2); the other estimators' "
+                                                        "padded pass is cv_flow_inference_ragged");
+        CV_CHECK(n_utt >= 1 && n_utt <= 8, "cv_flow_solve_ragged: 1..8 utterances");
+        CV_CHECK(Tmax > 0 && n_timesteps > 0, "cv_flow_solve_ragged: Tmax and n_timesteps must be positive");
+        for (int u = 0; u < n_utt; ++u) CV_CHECK(len[u] >= 1 && len[u] <= Tmax, "cv_flow_solve_ragged: every length must be 1..Tmax");
+        FlowScope scope(m);
+        hipStream_t s = resolve(m, stream);
+        std::vector<int> len0((size_t)2 * n_utt);
+        for (int z = 0; z < 2 * n_utt; ++z) len0[z] = len[z % n_utt];
+        est_reserve(m, Tmax, 2 * n_utt);
+        m->cur_ulen = unet1_len_table(m, len0.data(), 2 * n_utt, s);
+        try { solve_euler(m, x, mu, spks, cond, Tmax, n_timesteps, 0, s, n_utt); } catch (...) { m->cur_ulen = nullptr; throw; }
+        m->cur_ulen = nullptr;
     });
 }
 int cv_flow_inference_ragged(cv_flow* m, int32_t n_utt, const int32_t* token_ids, const int32_t* n_tok, const float* prompt_feat, const int32_t* mel_len1,

@@ -234,13 +234,26 @@ int cv_flow_estimator(cv_flow* m, const float* x, const float* mask, const float
 /* The same with a PADDED mask (the reference's estimator takes one, flow/decoder.py:405-494: every block multiplies by it, the attention bias is built
  * from it): mask row b = key_len[b] ones followed by zeros (HOST int32 [2], 1..T).  A row's valid positions come out as they would for that row alone
  * at its own length - the convolutions are causal, norms / linears per position, and the attention takes key_len[b] as the row's key count - and the
- * padded positions are zero (`output * mask`).  key_len == NULL: cv_flow_estimator. */
+ * padded positions are zero (`output * mask`).  key_len == NULL: cv_flow_estimator.
+ * A handle of the CosyVoice-300M U-Net (cfg.estimator == 2) keeps the same contract although that estimator is not causal: see cv_flow_solve_ragged. */
 int cv_flow_estimator_masked(cv_flow* m, const float* x, const float* mask, const int32_t* key_len, const float* mu, const float* t, const float* spks,
                              const float* cond, int32_t T, int32_t streaming, float* out, void* stream);
 /* ConditionalCFM.solve_euler for ONE utterance (flow/flow_matching.py:71-124; cosine t schedule, classifier-free guidance at cfg.cfg_rate, the estimator the handle
  * was built with): x [T][mel] dev fp32 CHANNEL-LAST - in: the initial noise z (with whatever the caller's flow cache wrote over its head), out: the mel; mu, cond
  * [T][mel] channel-last, spks [mel].  The n_timesteps estimator evaluations are one hipGraph from the second call of a shape on (option "use_graph"). */
 int cv_flow_solve(cv_flow* m, float* x, const float* mu, const float* spks, const float* cond, int32_t T, int32_t n_timesteps, void* stream);
+/* The same for n_utt (1..8) utterances of DIFFERENT lengths in one padded pass of the CosyVoice-300M U-Net (a handle with cfg.estimator == 2 only;
+ * flow/flow_matching.py:71-124 over flow/decoder.py:210-291): x, mu, cond dev fp32 [n_utt][Tmax][mel] channel-last and zero behind len[i], spks [n_utt][mel],
+ * len HOST int32 [n_utt], each 1..Tmax.  The estimator sees 2 n_utt rows (the guidance pair of every utterance) and issues the launches of ONE utterance.
+ * Contract - the one of cv_flow_estimator_masked: an utterance's frames 0 .. len[i] come out bit-identical to cv_flow_solve on it alone at T = len[i],
+ * whatever shares the pass and whatever Tmax is; the frames behind them stay as they came in (zero).  This estimator is not causal (centred convolutions,
+ * stride-2 / transposed convolutions, GroupNorm over channels x time), so every place the reference multiplies by the mask zeroes the padded frames here as well,
+ * attention takes a key count per row and resolution level (level k + 1 holds (len_k - 1) / 2 + 1 frames, the reference's mask[:, :, ::2]) - and GroupNorm takes
+ * its statistics over a row's OWN frames.  That last point deliberately differs from the reference's padded form, whose GroupNorm averages over the padded
+ * length and therefore does not reproduce its own batch-1 result.  Bad arguments (a null pointer, n_utt outside 1..8, a length outside 1..Tmax, a handle of
+ * another estimator) are errors with a message.  Padded passes are not captured as graphs. */
+int cv_flow_solve_ragged(cv_flow* m, int32_t n_utt, float* x, const float* mu, const float* spks, const float* cond, const int32_t* len, int32_t Tmax,
+                         int32_t n_timesteps, void* stream);
 /* B5: flow.inference(token ++ prompt_token, prompt_feat, embedding, streaming, finalize) -> mel[1,80,mel_len2]
  * (flow/flow.py:235-281 + flow_matching.py:71-124,203-227).  token_ids: dev int32 [n_tok] = prompt tokens then new tokens;
  * prompt_feat: dev [mel_len1,80]; embedding: dev [spk_dim]; noise_cl: dev [>=T,80] = CausalConditionalCFM.rand_noise
@@ -250,7 +263,8 @@ int cv_flow_inference(cv_flow* m, const int32_t* token_ids, int32_t n_tok, const
 /* The same for n_utt (1..8) utterances of EQUAL shape (token count, prompt frames) in one pass: token_ids dev [n_utt][n_tok], prompt_feat dev
  * [n_utt][mel_len1][80], embedding dev [n_utt][spk_dim], mel_out dev [n_utt][80][T - mel_len1].  The encoder runs per utterance, the CFM Euler solve
  * once over all of them (estimator batch rows = 2 x n_utt); each utterance's result is what cv_flow_inference gives for it alone
- * (the reference's own contract for batched flow, flow/flow.py:246).  CausalConditionalDecoder estimator only. */
+ * (the reference's own contract for batched flow, flow/flow.py:246).  CausalConditionalDecoder estimator only.
+ * cv_flow_inference, cv_flow_inference_batch and cv_flow_inference_ragged are errors on a handle with cfg.estimator == 2 (it holds no encoder). */
 /* The same for utterances of DIFFERENT lengths (the reference's padded batch with `mask`, flow/flow.py:236-281): token_ids dev, the utterances'
  * ids one after the other; n_tok / mel_len1 HOST arrays [n_utt]; prompt_feat dev, the prompts' [mel_len1[u]][80] blocks one after the other;
  * mel_out dev, the results' [80][mel_len2[u]] blocks one after the other; mel_len2_out HOST [n_utt].  Each result is bit-identical to the
