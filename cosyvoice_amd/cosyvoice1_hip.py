@@ -429,18 +429,27 @@ class EspnetEncoder(C1.EspnetEncoder):
             step.keep = step.keep + (l16, self._w16)
         return step
 
+    def _bind_args(self, state, bound):
+        """(key, rows, tabs) of a bind: the key names the state's buffers and the tables; rows / tabs are None when `bound` is that key already (nothing to rebind)."""
+        self._pos_tables(state.cap)                             # the tables cover every position the cache can hold: n_tab >= cap
+        key = (state.ident, self._pos_n)
+        if bound == key:
+            return key, None, None
+        n = self.n_layers
+        return key, (C.c_void_p * n)(*[r.data_ptr() for r in state.rows]), (C.c_void_p * n)(*[t.data_ptr() for t in self._pos_tab])
+
+    def _bind(self, step, state):
+        """cv_lm1_bind, when the state's cache rows or the tables were (re)allocated since `step` was last bound."""
+        key, rows, tabs = self._bind_args(state, step.bound)
+        if rows is not None:
+            step.lib.cv_lm1_bind(step.h, rows, tabs, C.c_int32(self._pos_n), C.c_int32(state.cap), stream_ptr(step.lib))
+            step.bound = key
+
     def fused_step(self, step, xs, state):
         """One decode row through `step` (make_step): cache row state.len of every layer is written, logits land in step.logits (valid until the next call)."""
         K, t0 = self.k, state.len
         state.reserve(t0 + 1)
-        self._pos_tables(state.cap)                             # the tables cover every position the cache can hold: n_tab >= cap
-        key = (state.ident, self._pos_n)
-        if step.bound != key:
-            n = self.n_layers
-            rows = (C.c_void_p * n)(*[r.data_ptr() for r in state.rows])
-            tabs = (C.c_void_p * n)(*[t.data_ptr() for t in self._pos_tab])
-            step.lib.cv_lm1_bind(step.h, rows, tabs, C.c_int32(self._pos_n), C.c_int32(state.cap), stream_ptr(step.lib))
-            step.bound = key
+        self._bind(step, state)
         step.lib.cv_lm1_step(step.h, C.c_void_p(xs.data_ptr()), C.c_int32(t0), C.c_void_p(step.logits.data_ptr()), stream_ptr(step.lib))
         state.len += 1
         state.plan = None
@@ -451,14 +460,7 @@ class EspnetEncoder(C1.EspnetEncoder):
         request's bounds; the cache is grown ONCE for every position the loop can write (no rebinding while it runs)."""
         t0 = state.len
         state.reserve(t0 + int(sp.max_len) + 1)
-        self._pos_tables(state.cap)
-        key = (state.ident, self._pos_n)
-        if step.bound != key:
-            n = self.n_layers
-            rows = (C.c_void_p * n)(*[r.data_ptr() for r in state.rows])
-            tabs = (C.c_void_p * n)(*[t.data_ptr() for t in self._pos_tab])
-            step.lib.cv_lm1_bind(step.h, rows, tabs, C.c_int32(self._pos_n), C.c_int32(state.cap), stream_ptr(step.lib))
-            step.bound = key
+        self._bind(step, state)
         u = None if uniforms is None else uniforms.detach().to(torch.float32).cpu().contiguous()
         step.lib.cv_lm1_decode_begin(step.h, C.c_void_p(x_row.data_ptr()), C.c_int32(t0), C.byref(sp), C.c_void_p(emb_table.data_ptr()), C.c_int32(int(sp.max_len)),
                                      C.c_void_p(u.data_ptr()) if u is not None else None, C.c_int32(0 if u is None else u.numel()), stream_ptr(step.lib))
@@ -479,12 +481,8 @@ class EspnetEncoder(C1.EspnetEncoder):
 
     def batch_bind(self, step, slot, state):
         """The slot's cache rows and the tables, when either was (re)allocated since the slot was last bound (cv_lm1_batch_bind keeps the slot's position and request)."""
-        self._pos_tables(state.cap)
-        key = (state.ident, self._pos_n)
-        if step.slot_bound[slot] != key:
-            n = self.n_layers
-            rows = (C.c_void_p * n)(*[r.data_ptr() for r in state.rows])
-            tabs = (C.c_void_p * n)(*[t.data_ptr() for t in self._pos_tab])
+        key, rows, tabs = self._bind_args(state, step.slot_bound[slot])
+        if rows is not None:
             step.lib.cv_lm1_batch_bind(step.h, C.c_int32(slot), rows, tabs, C.c_int32(self._pos_n), C.c_int32(state.cap), stream_ptr(step.lib))
             step.slot_bound[slot] = key
 
@@ -594,6 +592,27 @@ class TransformerLM(C1.TransformerLM):
                 if st is not None:
                     st.lib.cv_lm1_set_option(st.h, name.encode(), C.c_int32(int(value)))
 
+    def _take_loop_step(self):
+        """A decode-step handle of the caller's own: from the pool, or a new one with the stage's options (made under the stage lock: not to be called holding it)."""
+        with self._pool_lock:
+            if self._loop_steps:
+                return self._loop_steps.pop()
+        with self.lock:
+            step = self.llm.make_step(self.decoder, bf16=self.w16)      # (make_step succeeded for self.step: same arguments)
+            for name, value in self._step_options.items():
+                step.lib.cv_lm1_set_option(step.h, name.encode(), C.c_int32(value))
+        return step
+
+    def _give_loop_step(self, step):
+        step.bound = None                                        # the next request binds its own cache rows
+        with self._pool_lock:
+            self._loop_steps.append(step)
+
+    def _sampling_c(self, min_len, max_len, seed):
+        """The device sampler's parameters of one request: top_p 0.8, top_k 25, win_size 10, tau_r 0.1 (the reference's ras_sampling defaults), one stop token."""
+        from .llm import SamplingC
+        return SamplingC(1 if self.sampling == "ras" else 0, self.eos_token, 1, min_len, max_len, 0.8, 25, 10, 0.1, seed, 1 if self._uniforms is not None else 0)
+
     def step_stat(self, name):
         """A counter (cv_lm1_stat) summed over the stage's handles that are at rest (the host-sampler handle + the pooled loop handles)."""
         with self._pool_lock:
@@ -648,7 +667,6 @@ class TransformerLM(C1.TransformerLM):
                                "this object has sampling=%r, fused_step=%r - use inference() per request" % (self.sampling, self.fused_step))
         if not 1 <= int(slots) <= 8:
             raise ValueError("TransformerLM.inference_batch: 1..8 slots, not %r" % (slots,))
-        from .llm import SamplingC
         jobs = []                                                    # (index, request, min_len, max_len, seed) in list order
         with self.lock:
             for i, kw in enumerate(requests):
@@ -661,15 +679,10 @@ class TransformerLM(C1.TransformerLM):
                 elif mark_end:
                     jobs.append((i, None, 0, 0, 0))
         nb = max(1, min(int(slots), sum(1 for j in jobs if j[1] is not None)))
-        with self._pool_lock:
-            step = self._loop_steps.pop() if self._loop_steps else None
+        step = self._take_loop_step()
         live = {}                                                    # slot -> [index, state, max_len, tokens yielded]
         try:
             with self.lock:
-                if step is None:
-                    step = self.llm.make_step(self.decoder, bf16=self.w16)
-                    for name, value in self._step_options.items():
-                        step.lib.cv_lm1_set_option(step.h, name.encode(), C.c_int32(value))
                 self.llm.batch_begin(step, nb)
             jobs.reverse()
             while jobs or live:
@@ -683,8 +696,7 @@ class TransformerLM(C1.TransformerLM):
                                 continue
                             lm_input, L, _ = self._lm_input(kw["text"], kw["prompt_text"], kw["prompt_speech_token"], kw["embedding"])
                             _, state = self.llm.forward_chunk(lm_input[:L - 1], None)      # prefill: all rows but the last, exactly as `inference`
-                            sp = SamplingC(1 if self.sampling == "ras" else 0, self.eos_token, 1, lo, hi, 0.8, 25, 10, 0.1, seed, 1 if self._uniforms is not None else 0)
-                            self.llm.batch_open(step, slot, lm_input[L - 1:L].contiguous(), state, sp, self.speech_emb, self._uniforms)
+                            self.llm.batch_open(step, slot, lm_input[L - 1:L].contiguous(), state, self._sampling_c(lo, hi, seed), self.speech_emb, self._uniforms)
                             live[slot] = [i, state, hi, 0]
                     out = {}
                     if live:
@@ -706,13 +718,10 @@ class TransformerLM(C1.TransformerLM):
                     for i in ended:
                         yield i, None
         finally:                                                     # also on GeneratorExit: an abandoned batch frees its slots and gives its handle back
-            if step is not None:
-                with self.lock:
-                    for slot in list(live):
-                        self.llm.batch_release(step, slot)
-                step.bound = None
-                with self._pool_lock:
-                    self._loop_steps.append(step)
+            with self.lock:
+                for slot in list(live):
+                    self.llm.batch_release(step, slot)
+            self._give_loop_step(step)
 
     @torch.inference_mode()
     def inference(self, text, text_len, prompt_text, prompt_text_len, prompt_speech_token, prompt_speech_token_len, embedding,
@@ -726,19 +735,12 @@ class TransformerLM(C1.TransformerLM):
         min_len, max_len = int(n_text * min_token_text_ratio), int(n_text * max_token_text_ratio)
         if isinstance(self.sampling, str) and self.fused_step and max_len > 0 and L >= 2:
             # the loop on the device: prefill all rows but the last through the chunk path, then the last row is the loop's first input
-            from .llm import SamplingC
-            with self._pool_lock:
-                step = self._loop_steps.pop() if self._loop_steps else None
+            step = self._take_loop_step()
             try:
                 with self.lock:
-                    if step is None:
-                        step = self.llm.make_step(self.decoder, bf16=self.w16)      # (make_step succeeded for self.step: same arguments)
-                        for name, value in self._step_options.items():
-                            step.lib.cv_lm1_set_option(step.h, name.encode(), C.c_int32(value))
                     self._request += 1
                     _, state = self.llm.forward_chunk(lm_input[:L - 1], None)
-                    sp = SamplingC(1 if self.sampling == "ras" else 0, self.eos_token, 1, min_len, max_len, 0.8, 25, 10, 0.1, self.seed + self._request,
-                                   1 if self._uniforms is not None else 0)
+                    sp = self._sampling_c(min_len, max_len, self.seed + self._request)
                     self.llm.loop_begin(step, lm_input[L - 1:L].contiguous(), state, sp, self.speech_emb, self._uniforms)
                 done, n_yield = False, 0
                 while not done and n_yield < max_len:
@@ -748,10 +750,7 @@ class TransformerLM(C1.TransformerLM):
                         yield t
                     n_yield += len(toks)
             finally:                                                 # also on GeneratorExit: an abandoned request gives its handle back
-                if step is not None:
-                    step.bound = None                                # the next request binds its own cache rows
-                    with self._pool_lock:
-                        self._loop_steps.append(step)
+                self._give_loop_step(step)
             return
         out_tokens, state, x = [], None, lm_input
         for i in range(max_len):

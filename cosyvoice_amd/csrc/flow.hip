@@ -892,7 +892,7 @@ static void estimator_forward(cv_flow* m, int T, int t_row, int t_rows_total, bo
 //
 // Padded passes (`len`: device int32 [levels][nz], row k = the valid frames of every batch row at resolution level k, unet1_len_table): this estimator is NOT causal -
 // the centred convolutions, the stride-2 / transposed convolutions and GroupNorm's statistics over time all let the frames behind a row's end into its valid frames.
-// What keeps them out: GroupNorm takes its statistics over a row's own frames and writes zeros behind them (group_norm_len), attention takes the level's lengths as key
+// What keeps them out: GroupNorm takes its statistics over a row's own frames and writes zeros behind them (group_norm() with `len`), attention takes the level's lengths as key
 // counts, and wherever the reference has `x * mask` without a GroupNorm after it the padded rows are zeroed (zero_tail_rows): the packed input, a stage's output after its
 // transformer blocks, and what the resampling convolutions write behind a row's new end.  A valid row then reads exactly what it reads behind the end of the row alone
 // (zeros), through the same kernels: its bits are those of the row alone at its own length.  The reference's padded form (flow/decoder.py:210-291) masks the same places
@@ -905,8 +905,7 @@ static void unet1_forward(cv_flow* m, int T, int t_row, int t_rows_total, bool t
     auto conv = [&](const Lin& l, const float* in, int Tn, float* out, const float* res) { conv_cl(l, in, Tn, Tn, nz, l.taps / 2, 1, out, ACT_NONE, 0.f, res, s); };
     int rl = 0;                              // resolution level of the stream: + 1 behind a Downsample1D, - 1 behind an Upsample1D
     auto gnorm = [&](const float* in, float* out, int Tn, const LN& ln, const float* col_add, long long col_add_batch) {
-        if (len) group_norm_len(in, out, nz, Tn, C, G, len + rl * nz, ln.g, ln.b, 1e-5f, ACT_MISH, col_add, col_add_batch, gn, s);
-        else group_norm(in, out, nz, Tn, C, G, ln.g, ln.b, 1e-5f, ACT_MISH, col_add, col_add_batch, gn, s);
+        group_norm(in, out, nz, Tn, C, G, ln.g, ln.b, 1e-5f, ACT_MISH, col_add, col_add_batch, gn, s, len ? len + rl * nz : nullptr);
     };
     auto ztail = [&](float* p, int Tn, int Cn) { if (len) zero_tail_rows(p, nz, Tn, Cn, len + rl * nz, s); };
     ztail(m->s_in.as<float>(), T, 4 * c.mel);                        // (the broadcast speaker vector is not zero behind a row's end)

@@ -17,6 +17,7 @@
 #include "api_common.h"
 #include "common.h"
 #include "llm_kernels.h"
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -699,134 +700,154 @@ hipStream_t resolve(cv_lm1* m, void* s) {
     return m->own_stream;
 }
 
-// W16: the bf16 copy of W (cv_lm1_use_bf16) or null
-void gemv(cv_lm1* m, int pro, const float* x, const float* g, const float* b, float eps, const float* W, const void* W16, const float* bias, const float* res, float* y, int layer,
-          int set_pos, int N, int K, int act, hipStream_t s) {
+// ---- the kernel form of a decode GEMV ---------------------------------------------------------------------------------------------------------------------
+// ONE table for the single-sequence step and the lock-step batch: a slot of the batch goes through the batched twin of the kernel the single step picks for the same
+// (N, K, dtype, prologue), and that is what keeps a slot's bits those of the single step.
+//   form             single sequence                             slots of the batch (NBT slots, G vectors in LDS at a time, longest input)
+enum Lm1Form {
+    LM1_F16_ROWS,   // lm1_gemv16_kernel<true, 8, 1, 4, false>     lm1_gemv16b_kernel<true, 8, 4, false, NBT, all, 1024>      bf16, 16-byte loads, 16 whole rows per workgroup
+    LM1_F16_SPLIT,  // lm1_gemv16_kernel<true, 2, 1, 4, true>      lm1_gemv16b_kernel<true, 2, 4, true, NBT, all, 1024>       bf16, 4 waves split K
+    LM1_F16_SPLIT8, // lm1_gemv16_kernel<true, 4, 1, 8, true>      lm1_gemv16b_kernel<true, 4, 8, true, NBT, two, 4096>       bf16, 8 waves split K
+    LM1_F32_ROWS,   // lm1_gemv16_kernel<false, 16, 1, 4, false>   lm1_gemv16b_kernel<false, 16, 4, false, NBT, all, 1024>    fp32, 16 whole rows per workgroup
+    LM1_U4,         // lm1_gemv_kernel<4, 4, W16, RPG>             lm1_gemvb_kernel<4, 4, W16, NBT, all, 1024>                a wave's share is at most 4 steps
+    LM1_U8_NW8,     // lm1_gemv_kernel<8, 8, W16, RPG>             lm1_gemvb_kernel<8, 8, W16, NBT, two, 4096>                8 waves, 8 steps each
+    LM1_U8          // lm1_gemv_kernel<8, 4, W16, RPG>             lm1_gemvb_kernel<16, 4, W16, NBT, two, 4096>               U = 8 in flight, NW = 4: the 16 steps of a wave's share
+};                  //                                                                                                       are what the batched kernel holds in registers (S = 16)
+struct Lm1Pick { Lm1Form form; int rows; bool rpg; };      // rows: output rows per workgroup; rpg: an lm1_gemv_kernel form (single sequence: rows times RPG, option "gemv_rows")
+
+Lm1Pick pick_form(bool h16, int wide16, int wide32, int pro, int N, int K) {
+    const int kp = kp_of(K), steps = (kp + 63) / 64;
+    if (h16 && wide16 && kp % 128 == 0) {                      // 16-byte loads, whole rows per lane group (lm1_gemv16_kernel)
+        const int st = kp / 128;
+        if (st <= 8 && N >= 2048) return {LM1_F16_ROWS, 16, false};
+        if (st <= 8) return {LM1_F16_SPLIT, 4, false};
+        if (st <= 32 && pro == LM1_PRO_NONE) return {LM1_F16_SPLIT8, 4, false};
+    }
+    if (!h16 && wide32 && kp % 64 == 0 && kp <= 1024 && N >= 2048) return {LM1_F32_ROWS, 16, false};     // fp32 matrices, whole rows per lane group
+    if (steps <= 16) return {LM1_U4, 4, true};
+    if (pro == LM1_PRO_NONE && N <= 2048) return {LM1_U8_NW8, 4, true};
+    return {LM1_U8, 4, true};
+}
+
+// What a step works on: one sequence, or the nb slots of the batch - a slot's row one row width after the previous slot's.
+struct Lm1Seq {
+    int nb;                                    // 0: the single sequence (cv_lm1_step / cv_lm1_decode); 1..8: the slots of cv_lm1_batch_*
+    Lm1Dyn* dyn; DecodeState* st; float *x0, *x1, *h, *ff, *part;
+};
+// ... and what the device loop adds (decode_step): sampling parameters, emitted tokens, the next input row, logits, injected uniforms
+struct Lm1Loop { SampleParams* sp; int* tokens; float *xin, *logits, *uniforms; const float* emb_table; int tok_cap, uni_cap; };
+Lm1Seq seq_single(cv_lm1* m) { return {0, m->dyn.as<Lm1Dyn>(), m->dstate.as<DecodeState>(), m->x0.as<float>(), m->x1.as<float>(), m->h.as<float>(), m->ff.as<float>(), m->part.as<float>()}; }
+Lm1Loop loop_single(cv_lm1* m) { return {m->dsp.as<SampleParams>(), m->dtokens.as<int>(), m->xin.as<float>(), m->dlogits.as<float>(), m->duniforms.as<float>(), m->emb_table, m->max_tokens, 0}; }
+Lm1Seq seq_batch(cv_lm1* m) {
+    cv_lm1::Batch& B = m->batch;
+    return {B.nb, B.dyns.as<Lm1Dyn>(), B.sts.as<DecodeState>(), B.x0.as<float>(), B.x1.as<float>(), B.h.as<float>(), B.ff.as<float>(), B.part.as<float>()};
+}
+Lm1Loop loop_batch(cv_lm1* m) {
+    cv_lm1::Batch& B = m->batch;
+    return {B.sps.as<SampleParams>(), B.tokens.as<int>(), B.xin.as<float>(), B.logits.as<float>(), B.uniforms.as<float>(), B.emb_table, B.tok_cap, B.uni_cap};
+}
+
+template <int NBT>
+void gemvb_n(Lm1Pick f, bool h16, const Lm1BGemvArgs& q, hipStream_t s) {
+    constexpr int GA = NBT, GB = NBT < 2 ? NBT : 2;            // slots' vectors in LDS at a time: all (K <= 1024) / two (K <= 4096)
+    const dim3 grid((unsigned)((q.a.N + f.rows - 1) / f.rows));
+#define LM1_GEMV16B(W16_, STEPS_, NW_, KSPLIT_, G_, KW_) hipLaunchKernelGGL((lm1_gemv16b_kernel<W16_, STEPS_, NW_, KSPLIT_, NBT, G_, KW_>), grid, dim3(64 * NW_), 0, s, q)
+#define LM1_GEMVB(S_, NW_, G_, KW_) do { if (h16) hipLaunchKernelGGL((lm1_gemvb_kernel<S_, NW_, true, NBT, G_, KW_>), grid, dim3(64 * NW_), 0, s, q); \
+                                         else hipLaunchKernelGGL((lm1_gemvb_kernel<S_, NW_, false, NBT, G_, KW_>), grid, dim3(64 * NW_), 0, s, q); } while (0)
+    switch (f.form) {
+    case LM1_F16_ROWS:   LM1_GEMV16B(true, 8, 4, false, GA, 1024); break;
+    case LM1_F16_SPLIT:  LM1_GEMV16B(true, 2, 4, true, GA, 1024); break;
+    case LM1_F16_SPLIT8: LM1_GEMV16B(true, 4, 8, true, GB, LM1_MAX_K); break;
+    case LM1_F32_ROWS:   LM1_GEMV16B(false, 16, 4, false, GA, 1024); break;
+    case LM1_U4:         LM1_GEMVB(4, 4, GA, 1024); break;
+    case LM1_U8_NW8:     LM1_GEMVB(8, 8, GB, LM1_MAX_K); break;
+    case LM1_U8:         LM1_GEMVB(16, 4, GB, LM1_MAX_K); break;
+    }
+#undef LM1_GEMVB
+#undef LM1_GEMV16B
+}
+
+// One decode GEMV on q's sequence or slots (sx / sres / sy: floats between two slots' x / res / y).  W16: the bf16 copy of W (cv_lm1_use_bf16) or null
+void gemv(cv_lm1* m, const Lm1Seq& q, int pro, const float* x, long long sx, const float* g, const float* b, float eps, const float* W, const void* W16, const float* bias,
+          const float* res, long long sres, float* y, long long sy, int layer, int set_pos, int N, int K, int act, hipStream_t s) {
     CV_CHECK(K % 4 == 0 && K <= LM1_MAX_K && (pro != LM1_PRO_LN || K <= 1024), "cv_lm1: a GEMV input of up to 4096 floats (1024 under the LayerNorm prologue), K % 4 == 0");
     const bool h16 = m->w16 && W16 != nullptr;
-    Lm1GemvArgs a{x, g, b, eps, h16 ? reinterpret_cast<const float*>(W16) : W, (long long)kp_of(K), bias, res, y, m->dyn.as<Lm1Dyn>(), layer, set_pos, m->dstate.as<DecodeState>(), N, K, kp_of(K), act, pro};
-    const int steps = (kp_of(K) + 63) / 64;
-    const int rpg = h16 ? m->rows16 : m->rows32;
-    const dim3 grid((unsigned)((N + 4 * rpg - 1) / (4 * rpg)));
-#define LM1_GEMV(U_, NW_, W16_, RPG_) hipLaunchKernelGGL((lm1_gemv_kernel<U_, NW_, W16_, RPG_>), grid, dim3(64 * NW_), 0, s, a)
-#define LM1_GEMV_R(U_, NW_, W16_) do { if (rpg == 4) LM1_GEMV(U_, NW_, W16_, 4); else if (rpg == 2) LM1_GEMV(U_, NW_, W16_, 2); else LM1_GEMV(U_, NW_, W16_, 1); } while (0)
-    if (h16 && m->wide16 && kp_of(K) % 128 == 0) {             // 16-byte loads, whole rows per lane group (lm1_gemv16_kernel)
-        const int st = kp_of(K) / 128;
-        if (st <= 8 && N >= 2048) { hipLaunchKernelGGL((lm1_gemv16_kernel<true, 8, 1, 4, false>), dim3((unsigned)((N + 15) / 16)), dim3(256), 0, s, a); return; }
-        if (st <= 8) { hipLaunchKernelGGL((lm1_gemv16_kernel<true, 2, 1, 4, true>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, a); return; }
-        if (st <= 32 && pro == LM1_PRO_NONE) { hipLaunchKernelGGL((lm1_gemv16_kernel<true, 4, 1, 8, true>), dim3((unsigned)((N + 3) / 4)), dim3(512), 0, s, a); return; }
-    }
-    if (!h16 && m->wide32 && kp_of(K) % 64 == 0 && kp_of(K) <= 1024 && N >= 2048) {      // fp32 matrices, whole rows per lane group, 16 rows per workgroup
-        hipLaunchKernelGGL((lm1_gemv16_kernel<false, 16, 1, 4, false>), dim3((unsigned)((N + 15) / 16)), dim3(256), 0, s, a); return;
-    }
-    if (h16) {
-        if (steps <= 16) LM1_GEMV_R(4, 4, true);
-        else if (pro == LM1_PRO_NONE && N <= 2048) LM1_GEMV_R(8, 8, true);
-        else LM1_GEMV_R(8, 4, true);
+    const Lm1Pick f = pick_form(h16, m->wide16, m->wide32, pro, N, K);
+    Lm1GemvArgs a{x, g, b, eps, h16 ? reinterpret_cast<const float*>(W16) : W, (long long)kp_of(K), bias, res, y, q.nb ? nullptr : q.dyn, layer, set_pos, q.nb ? nullptr : q.st, N, K, kp_of(K), act, pro};
+    if (q.nb) {
+        const Lm1BGemvArgs qa{a, sx, sres, sy, q.dyn, q.st, q.nb};
+        if (q.nb == 1) gemvb_n<1>(f, h16, qa, s);
+        else if (q.nb == 2) gemvb_n<2>(f, h16, qa, s);
+        else if (q.nb <= 4) gemvb_n<4>(f, h16, qa, s);
+        else gemvb_n<8>(f, h16, qa, s);
         return;
     }
-    if (steps <= 16) LM1_GEMV_R(4, 4, false);
-    else if (pro == LM1_PRO_NONE && N <= 2048) LM1_GEMV_R(8, 8, false);
-    else LM1_GEMV_R(8, 4, false);
+    const int rpg = !f.rpg ? 1 : h16 ? m->rows16 : m->rows32;
+    const dim3 grid((unsigned)((N + f.rows * rpg - 1) / (f.rows * rpg)));
+#define LM1_GEMV16(W16_, STEPS_, NW_, KSPLIT_) hipLaunchKernelGGL((lm1_gemv16_kernel<W16_, STEPS_, 1, NW_, KSPLIT_>), grid, dim3(64 * NW_), 0, s, a)
+#define LM1_GEMV(U_, NW_, W16_, RPG_) hipLaunchKernelGGL((lm1_gemv_kernel<U_, NW_, W16_, RPG_>), grid, dim3(64 * NW_), 0, s, a)
+#define LM1_GEMV_R(U_, NW_, W16_) do { if (rpg == 4) LM1_GEMV(U_, NW_, W16_, 4); else if (rpg == 2) LM1_GEMV(U_, NW_, W16_, 2); else LM1_GEMV(U_, NW_, W16_, 1); } while (0)
+#define LM1_GEMV_H(U_, NW_) do { if (h16) LM1_GEMV_R(U_, NW_, true); else LM1_GEMV_R(U_, NW_, false); } while (0)
+    switch (f.form) {
+    case LM1_F16_ROWS:   LM1_GEMV16(true, 8, 4, false); break;
+    case LM1_F16_SPLIT:  LM1_GEMV16(true, 2, 4, true); break;
+    case LM1_F16_SPLIT8: LM1_GEMV16(true, 4, 8, true); break;
+    case LM1_F32_ROWS:   LM1_GEMV16(false, 16, 4, false); break;
+    case LM1_U4:         LM1_GEMV_H(4, 4); break;
+    case LM1_U8_NW8:     LM1_GEMV_H(8, 8); break;
+    case LM1_U8:         LM1_GEMV_H(8, 4); break;
+    }
+#undef LM1_GEMV_H
 #undef LM1_GEMV_R
 #undef LM1_GEMV
+#undef LM1_GEMV16
 }
 
 // The decode attention of one layer: nb == 0 is the single-sequence launch on dyn[0], nb >= 1 the batched one (blockIdx.z = slot, a slot's partials heads * LM1_SPLITS * 66
-// floats after the previous slot's).  Shared by step_body, batch_step and the kernel's test entry point (cv_lm1_attention).
+// floats after the previous slot's).  Shared by walk() and the kernel's test entry point (cv_lm1_attention).
 void launch_attn(const Lm1Dyn* dyn, int layer, int d, int heads, float scale, float* part, int nb, hipStream_t s) {
     Lm1AttnArgs aa{dyn, layer, d, heads, scale, part};
     if (nb > 0) { aa.slot_part = (long long)heads * LM1_SPLITS * 66; aa.batched = 1; }
     hipLaunchKernelGGL(lm1_attn_kernel, dim3(heads, LM1_SPLITS, nb > 0 ? nb : 1), dim3(256), 0, s, aa);
 }
 
-// everything of a step after its first kernel
-void step_body(cv_lm1* m, float* logits, hipStream_t s) {
-    const int d = m->d;
-    float* x0 = m->x0.as<float>(); float* x1 = m->x1.as<float>(); float* h = m->h.as<float>(); float* ff = m->ff.as<float>(); float* part = m->part.as<float>();
-    hipLaunchKernelGGL(lm1_norm_kernel, dim3(1), dim3(64), 0, s, Lm1NormArgs{h, x0, m->embed_g, m->embed_beta, 1e-5f, m->xscale, d, m->act});
-    for (int i = 0; i < m->n_layers; ++i) {
-        const Lm1Layer& L = m->L[i];
-        const cv_lm1::L16 H = m->w16 ? m->L16s[i] : cv_lm1::L16{};
-        gemv(m, LM1_PRO_LN, x0, L.ln1_g, L.ln1_b, 1e-12f, L.w_qkv, H.w_qkv, L.b_qkv, nullptr, nullptr, i, -1, 4 * d, d, ACT_NONE, s);
-        launch_attn(m->dyn.as<Lm1Dyn>(), i, d, m->heads, 0.125f, part, 0, s);
-        gemv(m, LM1_PRO_MERGE, part, nullptr, nullptr, 0.f, L.w_out, H.w_out, L.b_out, x0, x1, -1, -1, d, d, ACT_NONE, s);
-        gemv(m, LM1_PRO_LN, x1, L.ln2_g, L.ln2_b, 1e-12f, L.w1, H.w1, L.b1, nullptr, ff, -1, -1, m->ffn, d, m->act, s);
-        gemv(m, LM1_PRO_NONE, ff, nullptr, nullptr, 0.f, L.w2, H.w2, L.b2, x1, x0, -1, -1, d, m->ffn, ACT_NONE, s);
-    }
-    gemv(m, LM1_PRO_LN, x0, m->after_g, m->after_b, 1e-5f, m->dec_w, m->dec_w16, m->dec_b, nullptr, logits, -1, -1, m->n_out, d, ACT_NONE, s);
-}
-
-// ---- the batched step ---------------------------------------------------------------------------------------------------------------------------------------
-// gemv() for the slots of the batch: the SAME choice of kernel form per (N, K, dtype, prologue) - that is what keeps a slot's bits those of the single step.
-template <int NBT>
-void gemvb_n(cv_lm1* m, const Lm1BGemvArgs& q, bool h16, int pro, int N, int K, hipStream_t s) {
-    constexpr int GA = NBT, GB = NBT < 2 ? NBT : 2;            // slots' vectors in LDS at a time: all (K <= 1024) / two (K <= 4096)
-    const int kp = kp_of(K), steps = (kp + 63) / 64;
-    if (h16 && m->wide16 && kp % 128 == 0) {
-        const int st = kp / 128;
-        if (st <= 8 && N >= 2048) { hipLaunchKernelGGL((lm1_gemv16b_kernel<true, 8, 4, false, NBT, GA, 1024>), dim3((unsigned)((N + 15) / 16)), dim3(256), 0, s, q); return; }
-        if (st <= 8) { hipLaunchKernelGGL((lm1_gemv16b_kernel<true, 2, 4, true, NBT, GA, 1024>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, q); return; }
-        if (st <= 32 && pro == LM1_PRO_NONE) { hipLaunchKernelGGL((lm1_gemv16b_kernel<true, 4, 8, true, NBT, GB, LM1_MAX_K>), dim3((unsigned)((N + 3) / 4)), dim3(512), 0, s, q); return; }
-    }
-    if (!h16 && m->wide32 && kp % 64 == 0 && kp <= 1024 && N >= 2048) {
-        hipLaunchKernelGGL((lm1_gemv16b_kernel<false, 16, 4, false, NBT, GA, 1024>), dim3((unsigned)((N + 15) / 16)), dim3(256), 0, s, q); return;
-    }
-    const dim3 grid((unsigned)((N + 3) / 4));
-    if (h16) {
-        if (steps <= 16) hipLaunchKernelGGL((lm1_gemvb_kernel<4, 4, true, NBT, GA, 1024>), grid, dim3(256), 0, s, q);
-        else if (pro == LM1_PRO_NONE && N <= 2048) hipLaunchKernelGGL((lm1_gemvb_kernel<8, 8, true, NBT, GB, LM1_MAX_K>), grid, dim3(512), 0, s, q);
-        else hipLaunchKernelGGL((lm1_gemvb_kernel<16, 4, true, NBT, GB, LM1_MAX_K>), grid, dim3(256), 0, s, q);
-        return;
-    }
-    if (steps <= 16) hipLaunchKernelGGL((lm1_gemvb_kernel<4, 4, false, NBT, GA, 1024>), grid, dim3(256), 0, s, q);
-    else if (pro == LM1_PRO_NONE && N <= 2048) hipLaunchKernelGGL((lm1_gemvb_kernel<8, 8, false, NBT, GB, LM1_MAX_K>), grid, dim3(512), 0, s, q);
-    else hipLaunchKernelGGL((lm1_gemvb_kernel<16, 4, false, NBT, GB, LM1_MAX_K>), grid, dim3(256), 0, s, q);
-}
-
-void gemvb(cv_lm1* m, int pro, const float* x, long long sx, const float* g, const float* b, float eps, const float* W, const void* W16, const float* bias, const float* res, long long sres,
-           float* y, long long sy, int layer, int set_pos, int N, int K, int act, hipStream_t s) {
-    CV_CHECK(K % 4 == 0 && K <= LM1_MAX_K && (pro != LM1_PRO_LN || K <= 1024), "cv_lm1: a GEMV input of up to 4096 floats (1024 under the LayerNorm prologue), K % 4 == 0");
-    cv_lm1::Batch& B = m->batch;
-    const bool h16 = m->w16 && W16 != nullptr;
-    Lm1BGemvArgs q{};
-    q.a = Lm1GemvArgs{x, g, b, eps, h16 ? reinterpret_cast<const float*>(W16) : W, (long long)kp_of(K), bias, res, y, nullptr, layer, set_pos, nullptr, N, K, kp_of(K), act, pro};
-    q.sx = sx; q.sres = sres; q.sy = sy; q.dyns = B.dyns.as<Lm1Dyn>(); q.sts = B.sts.as<DecodeState>(); q.nb = B.nb;
-    if (B.nb == 1) gemvb_n<1>(m, q, h16, pro, N, K, s);
-    else if (B.nb == 2) gemvb_n<2>(m, q, h16, pro, N, K, s);
-    else if (B.nb <= 4) gemvb_n<4>(m, q, h16, pro, N, K, s);
-    else gemvb_n<8>(m, q, h16, pro, N, K, s);
-}
-
-// one lock-step step of every active slot: the launches of cv_lm1_decode's step, each of them over the slots
-void batch_step(cv_lm1* m, hipStream_t s) {
-    cv_lm1::Batch& B = m->batch;
-    const int d = m->d, nb = B.nb;
+// everything of a step after its first kernel (the input layer's Linear: q.h), for the single sequence and for the slots of the batch
+void walk(cv_lm1* m, const Lm1Seq& q, float* logits, hipStream_t s) {
+    const int d = m->d, ffn = m->ffn;
     const long long sp = (long long)m->heads * LM1_SPLITS * 66;
-    float* x0 = B.x0.as<float>(); float* x1 = B.x1.as<float>(); float* h = B.h.as<float>(); float* ff = B.ff.as<float>(); float* part = B.part.as<float>();
-    Lm1Dyn* dyns = B.dyns.as<Lm1Dyn>();
-    gemvb(m, LM1_PRO_NONE, B.xin.as<float>(), m->d_in, nullptr, nullptr, 0.f, m->embed_w, m->embed_w16, m->embed_b, nullptr, 0, h, d, -1, -2, d, m->d_in, ACT_NONE, s);
-    Lm1NormArgs na{h, x0, m->embed_g, m->embed_beta, 1e-5f, m->xscale, d, m->act};
-    na.sx = d; na.sy = d; na.dyns = dyns;
-    hipLaunchKernelGGL(lm1_norm_kernel, dim3(nb), dim3(64), 0, s, na);
+    Lm1NormArgs na{q.h, q.x0, m->embed_g, m->embed_beta, 1e-5f, m->xscale, d, m->act};
+    if (q.nb) { na.sx = d; na.sy = d; na.dyns = q.dyn; }
+    hipLaunchKernelGGL(lm1_norm_kernel, dim3(q.nb ? q.nb : 1), dim3(64), 0, s, na);
     for (int i = 0; i < m->n_layers; ++i) {
         const Lm1Layer& L = m->L[i];
         const cv_lm1::L16 H = m->w16 ? m->L16s[i] : cv_lm1::L16{};
-        gemvb(m, LM1_PRO_LN, x0, d, L.ln1_g, L.ln1_b, 1e-12f, L.w_qkv, H.w_qkv, L.b_qkv, nullptr, 0, nullptr, 0, i, -1, 4 * d, d, ACT_NONE, s);
-        launch_attn(dyns, i, d, m->heads, 0.125f, part, nb, s);
-        gemvb(m, LM1_PRO_MERGE, part, sp, nullptr, nullptr, 0.f, L.w_out, H.w_out, L.b_out, x0, d, x1, d, -1, -1, d, d, ACT_NONE, s);
-        gemvb(m, LM1_PRO_LN, x1, d, L.ln2_g, L.ln2_b, 1e-12f, L.w1, H.w1, L.b1, nullptr, 0, ff, m->ffn, -1, -1, m->ffn, d, m->act, s);
-        gemvb(m, LM1_PRO_NONE, ff, m->ffn, nullptr, nullptr, 0.f, L.w2, H.w2, L.b2, x1, d, x0, d, -1, -1, d, m->ffn, ACT_NONE, s);
+        gemv(m, q, LM1_PRO_LN, q.x0, d, L.ln1_g, L.ln1_b, 1e-12f, L.w_qkv, H.w_qkv, L.b_qkv, nullptr, 0, nullptr, 0, i, -1, 4 * d, d, ACT_NONE, s);
+        launch_attn(q.dyn, i, d, m->heads, 0.125f, q.part, q.nb, s);
+        gemv(m, q, LM1_PRO_MERGE, q.part, sp, nullptr, nullptr, 0.f, L.w_out, H.w_out, L.b_out, q.x0, d, q.x1, d, -1, -1, d, d, ACT_NONE, s);
+        gemv(m, q, LM1_PRO_LN, q.x1, d, L.ln2_g, L.ln2_b, 1e-12f, L.w1, H.w1, L.b1, nullptr, 0, q.ff, ffn, -1, -1, ffn, d, m->act, s);
+        gemv(m, q, LM1_PRO_NONE, q.ff, ffn, nullptr, nullptr, 0.f, L.w2, H.w2, L.b2, q.x1, d, q.x0, d, -1, -1, d, ffn, ACT_NONE, s);
     }
-    gemvb(m, LM1_PRO_LN, x0, d, m->after_g, m->after_b, 1e-5f, m->dec_w, m->dec_w16, m->dec_b, nullptr, 0, B.logits.as<float>(), m->n_out, -1, -1, m->n_out, d, ACT_NONE, s);
+    gemv(m, q, LM1_PRO_LN, q.x0, d, m->after_g, m->after_b, 1e-5f, m->dec_w, m->dec_w16, m->dec_b, nullptr, 0, logits, m->n_out, -1, -1, m->n_out, d, ACT_NONE, s);
+}
+
+// the first kernel of a step: the input layer's Linear on x (pos >= 0: the caller's row and position; -2: the parked rows and the positions of the device loop)
+void embed(cv_lm1* m, const Lm1Seq& q, const float* x, int set_pos, hipStream_t s) {
+    gemv(m, q, LM1_PRO_NONE, x, m->d_in, nullptr, nullptr, 0.f, m->embed_w, m->embed_w16, m->embed_b, nullptr, 0, q.h, m->d, -1, set_pos, m->d, m->d_in, ACT_NONE, s);
+}
+
+// one step of the device loop (cv_lm1_decode; cv_lm1_batch_decode: a lock-step step of every active slot): the step on the parked input, the sampler, the advance
+void decode_step(cv_lm1* m, const Lm1Seq& q, const Lm1Loop& l, hipStream_t s) {
+    embed(m, q, l.xin, -2, s);
+    walk(m, q, l.logits, s);
     SampleArgs sa{};
-    sa.logits = B.logits.as<float>(); sa.V = m->n_out; sa.sp = B.sps.as<SampleParams>(); sa.uniforms = B.uniforms.as<float>();
-    sa.st = B.sts.as<DecodeState>(); sa.tokens = B.tokens.as<int>(); sa.max_tokens = B.tok_cap;
-    sa.emb_table_f32 = B.emb_table; sa.emb_dim = m->d_in; sa.h_out = B.xin.as<float>();
-    sa.slot_logits = m->n_out; sa.slot_uniforms = B.uni_cap; sa.slot_tokens = B.tok_cap; sa.slot_h = m->d_in;
-    hipLaunchKernelGGL(sample_kernel, dim3(nb), dim3(1024), 0, s, sa);
-    hipLaunchKernelGGL(lm1_advance_slots_kernel, dim3(1), dim3(64), 0, s, sa.st, nb);
-    ++m->batch_steps;
+    sa.logits = l.logits; sa.V = m->n_out; sa.sp = l.sp; sa.uniforms = l.uniforms;
+    sa.st = q.st; sa.tokens = l.tokens; sa.max_tokens = l.tok_cap;
+    sa.emb_table_f32 = l.emb_table; sa.emb_dim = m->d_in; sa.h_out = l.xin;
+    if (q.nb) { sa.slot_logits = m->n_out; sa.slot_uniforms = l.uni_cap; sa.slot_tokens = l.tok_cap; sa.slot_h = m->d_in; }
+    hipLaunchKernelGGL(sample_kernel, dim3(q.nb ? q.nb : 1), dim3(1024), 0, s, sa);
+    if (q.nb) hipLaunchKernelGGL(lm1_advance_slots_kernel, dim3(1), dim3(64), 0, s, q.st, q.nb);
+    else hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, s, q.st);
+    ++(q.nb ? m->batch_steps : m->steps);
 }
 
 // a per-slot array grows (a request with a longer token budget than any before): the slots' contents move to the new pitch
@@ -838,6 +859,44 @@ void grow_slots(DevBuf& buf, size_t old_pitch, size_t new_pitch, int nb, hipStre
         CV_HIP(hipMemcpyAsync(static_cast<char*>(fresh.p) + i * new_pitch, static_cast<char*>(buf.p) + i * old_pitch, old_pitch, hipMemcpyDeviceToDevice, s));
     CV_HIP(hipStreamSynchronize(s));
     std::swap(buf.p, fresh.p); std::swap(buf.bytes, fresh.bytes);
+}
+
+// the device block of a sequence over caller-made cache rows and tables (cv_lm1_bind / cv_lm1_batch_bind; `who`: the entry point's name)
+// held_pos: the position of the request the slot holds, which the new cache must still cover (-1: none)
+Lm1Dyn checked_dyn(const char* who, const cv_lm1* m, float* const* rows, const float* const* tabs, int n_tab, int cap, int held_pos = -1) {
+    auto need = [&](bool ok, const char* what) { if (!ok) throw cv::Error(std::string(who) + ": " + what); };
+    need(cap >= 1 && cap <= LM1_SPLITS * LM1_MAX_KEYS_PER_SPLIT, "a cache of up to 32768 positions");
+    need(n_tab >= cap, "the relative-position tables must cover the cache (n_tab >= cap)");
+    need(held_pos < cap, "the new cache ends before the slot's position");
+    Lm1Dyn v{};
+    v.n_tab = n_tab;
+    for (int i = 0; i < m->n_layers; ++i) {
+        need(rows[i] && tabs[i] && aligned16(rows[i]) && aligned16(tabs[i]), "cache / table buffers present and 16B aligned");
+        v.rows[i] = rows[i]; v.tabs[i] = tabs[i];
+    }
+    return v;
+}
+
+// a request of the device loop (cv_lm1_decode_begin / cv_lm1_batch_open): its position and sampling parameters, checked (len_cap: the longest max_len the token
+// array takes - a slot's holds max_tokens) ...
+SampleParams checked_params(const char* who, const cv_lm1* m, int pos, int cap, const cv_sampling* sp, int max_tokens, int len_cap, const float* host_uniforms, int n_uniforms) {
+    auto need = [&](bool ok, const char* what) { if (!ok) throw cv::Error(std::string(who) + ": " + what); };
+    need(pos >= 0 && pos < cap && max_tokens >= 1, "position beyond the bound cache");
+    need(m->n_out <= 8192, "the device sampler holds at most 8192 logits");                 // (a batch: cv_lm1_batch_begin has refused it already)
+    need(sp->max_len > 0 && sp->max_len <= len_cap && sp->eos >= 0 && sp->eos + sp->n_stop <= m->n_out, "bad sampling parameters");
+    need(sp->mode == 0 || (sp->top_k > 0 && sp->top_k <= 64 && sp->win_size >= 0), "bad RAS parameters");
+    need(!sp->use_uniforms || (host_uniforms && n_uniforms >= 2), "use_uniforms needs the uniforms");
+    return SampleParams{sp->mode, sp->eos, sp->n_stop, sp->min_len, sp->max_len, sp->top_p, sp->top_k, sp->win_size, sp->tau_r, sp->use_uniforms, (unsigned long long)sp->seed};
+}
+// ... and parked on the device: the loop state (returned), the parameters, the first input row and the injected uniforms, at the given addresses
+DecodeState park_request(int pos, const SampleParams& hp, const float* x_row, int d_in, const float* host_uniforms, int n_uniforms, DecodeState* dst, SampleParams* dsp, float* dxin,
+                         float* duniforms, hipStream_t s) {
+    DecodeState st{}; st.pos = pos; st.stop_token = -1;
+    CV_HIP(hipMemcpyAsync(dst, &st, sizeof(st), hipMemcpyHostToDevice, s));
+    CV_HIP(hipMemcpyAsync(dsp, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
+    CV_HIP(hipMemcpyAsync(dxin, x_row, (size_t)d_in * 4, hipMemcpyDeviceToDevice, s));
+    if (hp.use_uniforms) CV_HIP(hipMemcpyAsync(duniforms, host_uniforms, (size_t)std::min(n_uniforms, 2 * hp.max_len) * 4, hipMemcpyHostToDevice, s));
+    return st;                                                  // (the copies read stack / caller memory: the caller synchronises before it returns)
 }
 
 }  // namespace
@@ -901,14 +960,7 @@ int cv_lm1_use_bf16(cv_lm1* m, const cv_lm1_layer_bf16* layers, const void* embe
 int cv_lm1_bind(cv_lm1* m, float* const* rows, const float* const* tabs, int32_t n_tab, int32_t cap, void* stream) {
     return guarded([&] {
         CV_CHECK(m && rows && tabs, "cv_lm1_bind: null argument");
-        CV_CHECK(cap >= 1 && cap <= LM1_SPLITS * LM1_MAX_KEYS_PER_SPLIT, "cv_lm1_bind: a cache of up to 32768 positions");
-        CV_CHECK(n_tab >= cap, "cv_lm1_bind: the relative-position tables must cover the cache (n_tab >= cap)");
-        Lm1Dyn v{};
-        v.pos = 0; v.n_tab = n_tab;
-        for (int i = 0; i < m->n_layers; ++i) {
-            CV_CHECK(rows[i] && tabs[i] && aligned16(rows[i]) && aligned16(tabs[i]), "cv_lm1_bind: cache / table buffers present and 16B aligned");
-            v.rows[i] = rows[i]; v.tabs[i] = tabs[i];
-        }
+        const Lm1Dyn v = checked_dyn("cv_lm1_bind", m, rows, tabs, n_tab, cap);
         hipLaunchKernelGGL(lm1_bind_kernel, dim3(1), dim3(64), 0, resolve(m, stream), m->dyn.as<Lm1Dyn>(), v);
         m->cap = cap; m->bound = 1;
     });
@@ -920,14 +972,14 @@ int cv_lm1_step(cv_lm1* m, const float* x_row, int32_t pos, float* logits, void*
         CV_CHECK(m->bound, "cv_lm1_step: cv_lm1_bind first");
         CV_CHECK(pos >= 0 && pos < m->cap, "cv_lm1_step: position beyond the bound cache");
         hipStream_t s = resolve(m, stream);
-        // first kernel: the input layer's Linear on the caller's row; it publishes the position the rest of the step reads
-        gemv(m, LM1_PRO_NONE, x_row, nullptr, nullptr, 0.f, m->embed_w, m->embed_w16, m->embed_b, nullptr, m->h.as<float>(), -1, pos, m->d, m->d_in, ACT_NONE, s);
+        const Lm1Seq q = seq_single(m);
+        embed(m, q, x_row, pos, s);                             // the first kernel publishes the position the rest of the step reads
         ++m->steps;
-        if (!m->use_graph) { step_body(m, logits, s); return; }
+        if (!m->use_graph) { walk(m, q, logits, s); return; }
         if (!m->graph || m->graph_logits != logits || m->graph_stream != s) {
             std::lock_guard<std::recursive_mutex> lk(runtime_lock());
             if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
-            hipGraph_t g = capture_graph(s, [&] { step_body(m, logits, s); });
+            hipGraph_t g = capture_graph(s, [&] { walk(m, q, logits, s); });
             hipError_t e = hipGraphInstantiate(&m->graph, g, nullptr, nullptr, 0);
             (void)hipGraphDestroy(g);
             if (e != hipSuccess) { m->graph = nullptr; CV_HIP(e); }
@@ -948,26 +1000,15 @@ int cv_lm1_decode_begin(cv_lm1* m, const float* x_row, int32_t pos, const cv_sam
     return guarded([&] {
         CV_CHECK(m && x_row && sp && emb_table && aligned16(x_row) && aligned16(emb_table), "cv_lm1_decode_begin: null / unaligned argument");
         CV_CHECK(m->bound, "cv_lm1_decode_begin: cv_lm1_bind first");
-        CV_CHECK(pos >= 0 && pos < m->cap && max_tokens >= 1, "cv_lm1_decode_begin: position beyond the bound cache");
-        CV_CHECK(m->n_out <= 8192, "cv_lm1_decode_begin: the device sampler holds at most 8192 logits");
-        CV_CHECK(sp->max_len > 0 && sp->eos >= 0 && sp->eos + sp->n_stop <= m->n_out, "cv_lm1_decode_begin: bad sampling parameters");
-        CV_CHECK(sp->mode == 0 || (sp->top_k > 0 && sp->top_k <= 64 && sp->win_size >= 0), "cv_lm1_decode_begin: bad RAS parameters");
-        CV_CHECK(!sp->use_uniforms || (host_uniforms && n_uniforms >= 2), "cv_lm1_decode_begin: use_uniforms needs the uniforms");
+        const SampleParams hp = checked_params("cv_lm1_decode_begin", m, pos, m->cap, sp, max_tokens, INT_MAX, host_uniforms, n_uniforms);
         hipStream_t s = resolve(m, stream);
         m->dstate.ensure(sizeof(DecodeState)); m->dsp.ensure(sizeof(SampleParams)); m->dtokens.ensure((size_t)max_tokens * 4); m->xin.ensure((size_t)m->d_in * 4);
         m->dlogits.ensure((size_t)m->n_out * 4);
         m->max_tokens = max_tokens; m->emb_table = emb_table; m->host_tokens.assign(max_tokens, 0);
-        DecodeState st{}; st.pos = pos; st.stop_token = -1;
-        m->host_state = st;
-        const SampleParams hp{sp->mode, sp->eos, sp->n_stop, sp->min_len, sp->max_len, sp->top_p, sp->top_k, sp->win_size, sp->tau_r, sp->use_uniforms, (unsigned long long)sp->seed};
-        CV_HIP(hipMemcpyAsync(m->dstate.p, &st, sizeof(st), hipMemcpyHostToDevice, s));
-        CV_HIP(hipMemcpyAsync(m->dsp.p, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
-        CV_HIP(hipMemcpyAsync(m->xin.p, x_row, (size_t)m->d_in * 4, hipMemcpyDeviceToDevice, s));
-        if (sp->use_uniforms) {
-            m->duniforms.ensure((size_t)2 * sp->max_len * 4);
-            CV_HIP(hipMemcpyAsync(m->duniforms.p, host_uniforms, (size_t)std::min(n_uniforms, 2 * sp->max_len) * 4, hipMemcpyHostToDevice, s));
-        }
-        CV_HIP(hipStreamSynchronize(s));                        // the host copies above are stack / caller memory
+        if (sp->use_uniforms) m->duniforms.ensure((size_t)2 * sp->max_len * 4);
+        m->host_state = park_request(pos, hp, x_row, m->d_in, host_uniforms, n_uniforms, m->dstate.as<DecodeState>(), m->dsp.as<SampleParams>(), m->xin.as<float>(),
+                                     m->duniforms.as<float>(), s);
+        CV_HIP(hipStreamSynchronize(s));
         m->loop_open = 1;
     });
 }
@@ -978,20 +1019,11 @@ int cv_lm1_decode(cv_lm1* m, int32_t n_steps, int32_t* out_tokens, int32_t* n_ou
         CV_CHECK(m->loop_open, "cv_lm1_decode: cv_lm1_decode_begin first");
         CV_CHECK(m->host_state.done || m->host_state.pos + n_steps <= m->cap, "cv_lm1_decode: the bound cache ends before these steps do");
         hipStream_t s = resolve(m, stream);
-        DecodeState* st = m->dstate.as<DecodeState>();
         const int before = m->host_state.n_tokens;
-        for (int i = 0; i < n_steps; ++i) {
-            gemv(m, LM1_PRO_NONE, m->xin.as<float>(), nullptr, nullptr, 0.f, m->embed_w, m->embed_w16, m->embed_b, nullptr, m->h.as<float>(), -1, -2, m->d, m->d_in, ACT_NONE, s);
-            step_body(m, m->dlogits.as<float>(), s);
-            SampleArgs sa{};
-            sa.logits = m->dlogits.as<float>(); sa.V = m->n_out; sa.sp = m->dsp.as<SampleParams>(); sa.uniforms = m->duniforms.as<float>();
-            sa.st = st; sa.tokens = m->dtokens.as<int>(); sa.max_tokens = m->max_tokens;
-            sa.emb_table_f32 = m->emb_table; sa.emb_dim = m->d_in; sa.h_out = m->xin.as<float>();
-            hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(1024), 0, s, sa);
-            hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, s, st);
-            ++m->steps;
-        }
-        CV_HIP(hipMemcpyAsync(&m->host_state, st, sizeof(DecodeState), hipMemcpyDeviceToHost, s));
+        const Lm1Seq q = seq_single(m);
+        const Lm1Loop l = loop_single(m);
+        for (int i = 0; i < n_steps; ++i) decode_step(m, q, l, s);
+        CV_HIP(hipMemcpyAsync(&m->host_state, q.st, sizeof(DecodeState), hipMemcpyDeviceToHost, s));
         CV_HIP(hipMemcpyAsync(m->host_tokens.data(), m->dtokens.p, (size_t)m->max_tokens * 4, hipMemcpyDeviceToHost, s));
         CV_HIP(hipStreamSynchronize(s));
         CV_HIP(hipGetLastError());
@@ -1037,16 +1069,8 @@ int cv_lm1_batch_bind(cv_lm1* m, int32_t slot, float* const* rows, const float* 
         CV_CHECK(m && rows && tabs, "cv_lm1_batch_bind: null argument");
         CV_CHECK(m->batch.nb > 0, "cv_lm1_batch_bind: cv_lm1_batch_begin first");
         CV_CHECK(slot >= 0 && slot < m->batch.nb, "cv_lm1_batch_bind: slot out of range");
-        CV_CHECK(cap >= 1 && cap <= LM1_SPLITS * LM1_MAX_KEYS_PER_SPLIT, "cv_lm1_batch_bind: a cache of up to 32768 positions");
-        CV_CHECK(n_tab >= cap, "cv_lm1_batch_bind: the relative-position tables must cover the cache (n_tab >= cap)");
         cv_lm1::Slot& S = m->batch.slots[slot];
-        CV_CHECK(!S.open || S.host.done || S.host.pos < cap, "cv_lm1_batch_bind: the new cache ends before the slot's position");
-        Lm1Dyn v{};
-        v.n_tab = n_tab;
-        for (int i = 0; i < m->n_layers; ++i) {
-            CV_CHECK(rows[i] && tabs[i] && aligned16(rows[i]) && aligned16(tabs[i]), "cv_lm1_batch_bind: cache / table buffers present and 16B aligned");
-            v.rows[i] = rows[i]; v.tabs[i] = tabs[i];
-        }
+        const Lm1Dyn v = checked_dyn("cv_lm1_batch_bind", m, rows, tabs, n_tab, cap, S.open && !S.host.done ? S.host.pos : -1);
         hipStream_t s = resolve(m, stream);
         Lm1Dyn* dslot = m->batch.dyns.as<Lm1Dyn>() + slot;
         hipLaunchKernelGGL(lm1_bind_slot_kernel, dim3(1), dim3(64), 0, s, dslot, v);
@@ -1064,10 +1088,7 @@ int cv_lm1_batch_open(cv_lm1* m, int32_t slot, const float* x_row, int32_t pos, 
         cv_lm1::Slot& S = B.slots[slot];
         CV_CHECK(S.bound, "cv_lm1_batch_open: cv_lm1_batch_bind first");
         CV_CHECK(!S.open, "cv_lm1_batch_open: the slot holds a request (cv_lm1_batch_release first)");
-        CV_CHECK(pos >= 0 && pos < S.cap && max_tokens >= 1, "cv_lm1_batch_open: position beyond the bound cache");
-        CV_CHECK(sp->max_len > 0 && sp->max_len <= max_tokens && sp->eos >= 0 && sp->eos + sp->n_stop <= m->n_out, "cv_lm1_batch_open: bad sampling parameters");
-        CV_CHECK(sp->mode == 0 || (sp->top_k > 0 && sp->top_k <= 64 && sp->win_size >= 0), "cv_lm1_batch_open: bad RAS parameters");
-        CV_CHECK(!sp->use_uniforms || (host_uniforms && n_uniforms >= 2), "cv_lm1_batch_open: use_uniforms needs the uniforms");
+        const SampleParams hp = checked_params("cv_lm1_batch_open", m, pos, S.cap, sp, max_tokens, max_tokens, host_uniforms, n_uniforms);
         bool others = false;
         for (int i = 0; i < B.nb; ++i) others = others || B.slots[i].open;
         CV_CHECK(!others || B.emb_table == emb_table, "cv_lm1_batch_open: the slots of a batch share one embedding table");
@@ -1077,14 +1098,9 @@ int cv_lm1_batch_open(cv_lm1* m, int32_t slot, const float* x_row, int32_t pos, 
             const int cap = std::max(2 * sp->max_len, 2 * B.uni_cap); grow_slots(B.uniforms, (size_t)B.uni_cap * 4, (size_t)cap * 4, B.nb, s); B.uni_cap = cap;
         }
         B.host_tokens.resize((size_t)B.nb * B.tok_cap);
-        DecodeState st{}; st.pos = pos; st.stop_token = -1;
-        const SampleParams hp{sp->mode, sp->eos, sp->n_stop, sp->min_len, sp->max_len, sp->top_p, sp->top_k, sp->win_size, sp->tau_r, sp->use_uniforms, (unsigned long long)sp->seed};
-        CV_HIP(hipMemcpyAsync(B.sts.as<DecodeState>() + slot, &st, sizeof(st), hipMemcpyHostToDevice, s));
-        CV_HIP(hipMemcpyAsync(B.sps.as<SampleParams>() + slot, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
-        CV_HIP(hipMemcpyAsync(B.xin.as<float>() + (size_t)slot * m->d_in, x_row, (size_t)m->d_in * 4, hipMemcpyDeviceToDevice, s));
-        if (sp->use_uniforms)
-            CV_HIP(hipMemcpyAsync(B.uniforms.as<float>() + (size_t)slot * B.uni_cap, host_uniforms, (size_t)std::min(n_uniforms, 2 * sp->max_len) * 4, hipMemcpyHostToDevice, s));
         Lm1Dyn* dslot = B.dyns.as<Lm1Dyn>() + slot; DecodeState* sslot = B.sts.as<DecodeState>() + slot;      // (plain values for the launch: a launch captures its arguments by value)
+        const DecodeState st = park_request(pos, hp, x_row, m->d_in, host_uniforms, n_uniforms, sslot, B.sps.as<SampleParams>() + slot, B.xin.as<float>() + (size_t)slot * m->d_in,
+                                            B.uniforms.as<float>() + (size_t)slot * B.uni_cap, s);
         hipLaunchKernelGGL(lm1_slot_flag_kernel, dim3(1), dim3(64), 0, s, dslot, sslot, 1);
         CV_HIP(hipStreamSynchronize(s));                        // the host copies above are stack / caller memory
         S.open = 1; S.returned = 0; S.host = st; B.host_states[slot] = st; B.emb_table = emb_table; B.stream = s;
@@ -1105,7 +1121,9 @@ int cv_lm1_batch_decode(cv_lm1* m, int32_t n_steps, int32_t* out_tokens, int32_t
         CV_CHECK(any, "cv_lm1_batch_decode: no open slot (cv_lm1_batch_open first)");
         hipStream_t s = resolve(m, stream);
         B.stream = s;
-        for (int i = 0; i < n_steps; ++i) batch_step(m, s);
+        const Lm1Seq q = seq_batch(m);
+        const Lm1Loop l = loop_batch(m);
+        for (int i = 0; i < n_steps; ++i) decode_step(m, q, l, s);
         CV_HIP(hipMemcpyAsync(B.host_states.data(), B.sts.p, (size_t)B.nb * sizeof(DecodeState), hipMemcpyDeviceToHost, s));
         CV_HIP(hipMemcpyAsync(B.host_tokens.data(), B.tokens.p, (size_t)B.nb * B.tok_cap * 4, hipMemcpyDeviceToHost, s));
         CV_HIP(hipStreamSynchronize(s));
@@ -1179,7 +1197,7 @@ int cv_lm1_attention(int32_t nb, const float* const* rows, const float* const* t
 }
 
 namespace {
-// what both GEMV hooks refuse (gemv() / gemvb() themselves check K); `who` is the hook's name
+// what both GEMV hooks refuse (gemv() itself checks K); `who` is the hook's name
 void check_gemv_hook(const char* who, cv_lm1* m, int pro, const float* x, const float* g, const float* b, float eps, const float* W, const void* W16, const float* bias,
                      const float* res, const float* y, int N, int K, int act) {
     auto fail = [&](const char* what) { throw cv::Error(std::string(who) + ": " + what); };
@@ -1202,7 +1220,7 @@ int cv_lm1_gemv(cv_lm1* m, int32_t pro, const float* x, const float* g, const fl
                 int32_t N, int32_t K, int32_t act, void* stream) {
     return guarded([&] {
         check_gemv_hook("cv_lm1_gemv", m, pro, x, g, b, eps, W, W16, bias, res, y, N, K, act);
-        gemv(m, pro, x, g, b, eps, W, W16, bias, res, y, -1, -1, N, K, act, resolve(m, stream));
+        gemv(m, seq_single(m), pro, x, 0, g, b, eps, W, W16, bias, res, 0, y, 0, -1, -1, N, K, act, resolve(m, stream));
     });
 }
 
@@ -1223,7 +1241,7 @@ int cv_lm1_gemv_batch(cv_lm1* m, int32_t nb, uint32_t active_mask, int32_t pro, 
             }
         };
         flags(active_mask);
-        try { gemvb(m, pro, x, sx, g, b, eps, W, W16, bias, res, sres, y, sy, -1, -1, N, K, act, s); }
+        try { gemv(m, seq_batch(m), pro, x, sx, g, b, eps, W, W16, bias, res, sres, y, sy, -1, -1, N, K, act, s); }
         catch (...) { flags(0); throw; }
         flags(0);
     });

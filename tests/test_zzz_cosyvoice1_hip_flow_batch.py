@@ -46,6 +46,30 @@ def test_estimator_padded_rows_equal_the_rows_alone(lib, precision, lens):
         hd.forward(x, 1 - mask, mu, t, spks, cond)
 
 
+def test_generic_group_norm_form_on_padded_rows(lib):
+    """The GENERIC length-aware GroupNorm (group_stats_kernel / group_apply_kernel, LEN instantiation) through cv_flow_estimator_masked: the U-Net's own widths (C / 4 a
+    power of two) send every GroupNorm through the row-wise form, so this handle is 96 channels wide, the narrowest the generic form takes (C % 32 == 0 and C / 4 = 24
+    does not divide 256).  A group is cg = 12 channels and its slice count ceil(len * 12 / 8192): row 0's 700 frames make two slices (8400 elements), row 1's single
+    frame one - the rows of one launch differ in their slice count and the short row's second slice must do nothing.  Same contract and same equalities as above:
+    a row's valid frames are those of the row alone at its own length, the frames behind them exact zeros."""
+    import dataclasses
+    cfg = dataclasses.replace(CFG, est_ch=[96], est_mid=1)                  # (one level, one mid block: the arm under test needs no more)
+    hd = CK.EstimatorHandle(W.make_cv1_flow(cfg), "decoder.estimator.", cfg.est_heads, lib, "fp32")
+    lens = (700, 1)
+    T = max(lens)
+    gen = torch.Generator().manual_seed(5)
+    x, mu, cond = (torch.randn(2, 80, T, generator=gen) for _ in range(3))
+    spks, t = torch.randn(2, 80, generator=gen), torch.tensor([0.3, 0.8])
+    mask = (torch.arange(T).unsqueeze(0) < torch.tensor(lens).unsqueeze(1)).float().unsqueeze(1)
+    got = hd.forward(x, mask, mu, t, spks, cond).cpu()
+    for b, L in enumerate(lens):
+        two = lambda a: torch.stack([a[b], a[b]])
+        alone = hd.forward(two(x)[:, :, :L], torch.ones(2, 1, L), two(mu)[:, :, :L], two(t), two(spks), two(cond)[:, :, :L]).cpu()[0]
+        assert bool(torch.isfinite(alone).all()) and float(alone.abs().max()) > 0
+        assert torch.equal(got[b, :, :L], alone), (b, float((got[b, :, :L] - alone).abs().max()))
+        assert L == T or float(got[b, :, L:].abs().max()) == 0.0
+
+
 def _solve_inputs(hd, lens, seed=17):
     gen = torch.Generator().manual_seed(seed)
     put = lambda a: hd.lib.hook(a.to(hd.dev).contiguous())

@@ -1,5 +1,5 @@
 """The kernels of the CosyVoice-300M decode step (csrc/lm1.hip: lm1_attn_kernel, the lm1_gemv / lm1_gemv16 forms and their batched twins) against float64
-references, through the test entry points cv_lm1_attention, cv_lm1_gemv and cv_lm1_gemv_batch - the launch helpers of the step itself (launch_attn, gemv(), gemvb()).
+references, through the test entry points cv_lm1_attention, cv_lm1_gemv and cv_lm1_gemv_batch - the launch helpers of the step itself (launch_attn, gemv() for the single sequence and for the slots).
 
 Every operand is allocated at its exact size through lib.hook (under the emulator it ends flush against an inaccessible page); outputs carry a sentinel and spare tail
 elements, and exactly the problem's elements must have been written.  U = 2^-24 below.
