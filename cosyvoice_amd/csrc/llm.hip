@@ -47,6 +47,9 @@ struct cv_llm {
     int head_rows = 1;                                // rows per 16-lane group of the head GEMV (1: 411 workgroups, 2: 206)
     int head_waves = 4;                               // head_rows == 1: waves per workgroup of the head GEMV (4: 411 workgroups = 1.6 per CU; 7: 235 workgroups, one per CU) - option "head_waves" / CV_HEAD_WAVES
     int attn_splits = 8;
+    // down projection with its input staged once per workgroup in LDS (gemv_kernel<.., XLDS>: same bits, 4.9 -> 4.1 us per launch; 0 = every 16-lane group fetches its
+    // own copy).  A/B knob read from the environment when the handle is created, like batch_packed below.
+    int down_xlds = [] { const char* e = getenv("CV_DOWN_XLDS"); return (e && e[0] == '0') ? 0 : 1; }();
     // option "prefetch" (env CV_DECODE_PREFETCH): extra workgroups of the short decode kernels read the weights the bandwidth-bound kernels behind them
     // will stream (llm_kernels.h PrefetchArgs).  0 = off; 1 = attention fetches gate / up, o_proj fetches down; 2 = qkv fetches gate / up, attention
     // fetches down.  "prefetch_shift": dev knob (fetch for another consumer workgroup: breaks the XCD match).
@@ -342,7 +345,7 @@ struct ProfScope {
 static const bool g_gemv_shared_norm = [] { const char* e = getenv("CV_GEMV_SHARED_NORM"); return !(e && e[0] == '0'); }();
 
 // picks the instantiation from K (= 128 * steps): <=7 steps -> one wave per 4*ROWS rows; <=40 steps -> 4-way split-K
-static void gemv(const GemvArgs& a, int rows, hipStream_t s, int nsp = 0, int waves = 4) {
+static void gemv(const GemvArgs& a, int rows, hipStream_t s, int nsp = 0, int waves = 4, bool xlds = false) {
     const int steps = a.K / 128;
     if (nsp > 0) {                                   // o_proj over split-attention partials (rows == 1, K = heads * 64 <= 1024)
         CV_CHECK(steps <= 8 && rows == 1 && a.mode == 0 && !a.gamma && a.part, "gemv: partial-combine prologue is for the o_proj shape only");
@@ -381,6 +384,7 @@ static void gemv(const GemvArgs& a, int rows, hipStream_t s, int nsp = 0, int wa
     } else {
         CV_CHECK(!a.gamma, "gemv: fused RMSNorm needs the whole row in one wave (K <= 896)");
         if (rows == 2) hipLaunchKernelGGL((gemv_kernel<10, 2, 4>), grid, dim3(256), 0, s, a);
+        else if (xlds && a.mode == 0) hipLaunchKernelGGL((gemv_kernel<10, 1, 4, 0, true>), grid, dim3(256), 0, s, a);   // down: x staged once per workgroup (same bits)
         else           hipLaunchKernelGGL((gemv_kernel<10, 1, 4>), grid, dim3(256), 0, s, a);
     }
 }
@@ -434,7 +438,7 @@ static void llm_enqueue_step(cv_llm* m, hipStream_t s) {
             if (want(3)) { ProfScope ps(m, s, 3); gemv(gg, 2, s); }
             GemvArgs gd2{L.wdown, nullptr, act, h, c.hidden, c.inter, nullptr, 0.f, m->h2.as<float>(), 0, st};
             if (i == c.layers - 1 && m->only_cat < 0) gd2.advance = m->state.as<DecodeState>();
-            if (want(4)) { ProfScope ps(m, s, 4); gemv(gd2, 1, s); }
+            if (want(4)) { ProfScope ps(m, s, 4); gemv(gd2, 1, s, 0, 4, m->down_xlds != 0); }
             continue;
         }
 #endif
@@ -466,7 +470,7 @@ static void llm_enqueue_step(cv_llm* m, hipStream_t s) {
         if (want(3)) { ProfScope ps(m, s, 3); gemv(GemvArgs{L.wgu, nullptr, h, act, 2 * c.inter, c.hidden, L.ln2, c.rms_eps, nullptr, 1, st}, 2, s); }
         GemvArgs gd{L.wdown, nullptr, act, h, c.hidden, c.inter, nullptr, 0.f, h, 0, st};
         if (i == c.layers - 1 && m->only_cat < 0) gd.advance = m->state.as<DecodeState>();     // the step's last kernel also advances the KV length
-        if (want(4)) { ProfScope ps(m, s, 4); gemv(gd, 1, s); }
+        if (want(4)) { ProfScope ps(m, s, 4); gemv(gd, 1, s, 0, 4, m->down_xlds != 0); }
     }
 }
 

@@ -94,8 +94,17 @@ constexpr int ATTN_PART = 68;      // 64 unnormalised numerators + running max +
 // every lane first issues ALL of its weight loads (ROWS x STEPS x 16 B, non-temporal: each byte is read once per token),
 // then its slice of x (and gamma) straight from L2 into registers — no LDS staging, no barrier before the weights are in
 // flight.  RMSNorm statistics come from a 16-lane shuffle reduction (each group covers the whole row when WAVES == 1).
-template <int STEPS, int ROWS, int WAVES, int NSP = 0>
+// XLDS (down, K = inter <= 5120): the input is fetched ONCE per workgroup instead of once per 16-lane group.  Without it each of the 16 groups of a
+// workgroup loads its wave's K-slice of x - at K = 4864, 77.8 KB of x against 38.9 KB of weights through one CU, 20 load instructions per lane behind the
+// 10 of the weight rows, and per-CU ingest is what binds these kernels (see gemv_norm_kernel).  With it the 256 threads request x FIRST (5 float4 per
+// thread, ahead of the weight rows as in gemv_norm_kernel's XFIRST: vmcnt retires in issue order), park it in LDS while the weights are in flight and
+// read their xa / xb from there.  Same values into the same FMAs in the same order: the output has the bits of the plain form; 4.9 -> 4.1 us per launch
+// on MI355X (profiles/lm_chain_ab.txt).  LDS image: inside each 128-float step the 16 first halves (floats 8 sub .. 8 sub + 3) come first and the 16
+// second halves after them, so that a 16-lane group's ds_read_b128 covers one contiguous 256-byte bank row (x as it lies in memory would put lanes sub
+// and sub + 8 on the same banks: a 2-way conflict on every read); the four groups of a wave read the same addresses.
+template <int STEPS, int ROWS, int WAVES, int NSP = 0, bool XLDS = false>
 __global__ __launch_bounds__(WAVES * 64) void gemv_kernel(GemvArgs p) {
+    static_assert(!XLDS || (NSP == 0 && WAVES == 4 && STEPS % 2 == 0), "the LDS-staged input is for the 4-wave split-K form without a merge prologue; whole rounds of float4 per thread");
     __shared__ float part[WAVES][4][ROWS];
     // no `done` test here: it would put a dependent load in front of the weight stream; a finished request simply recomputes
     // into buffers nobody reads (sample / embed / advance are the kernels that honour `done`).
@@ -122,6 +131,13 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_kernel(GemvArgs p) {
             ml[q] = *reinterpret_cast<const float2*>(ph + q * ATTN_PART + 64);
         }
     }
+    constexpr int XR = XLDS ? STEPS / 2 : 1;                 // float4 per thread: XR * 256 of them cover K <= STEPS * WAVES * 128
+    u32x4 xq[XR];                                            // (a native vector: an array of float4 that lives across order_memory() goes to scratch)
+    if constexpr (XLDS) {
+#pragma unroll
+        for (int r = 0; r < XR; ++r) { const int i = tid + r * WAVES * 64; xq[r] = *reinterpret_cast<const u32x4*>(p.x + (i * 4 < p.K ? i * 4 : 0)); }   // unconditional, clamped
+        order_memory();                                      // the requests stay here, ahead of the weight rows
+    }
     u32x4 w[ROWS][STEPS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
@@ -137,7 +153,24 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_kernel(GemvArgs p) {
         }
     }
     float4 xa[STEPS], xb[STEPS];
-    if constexpr (NSP == 0) {
+    if constexpr (XLDS) {
+        __shared__ __attribute__((aligned(16))) float xl[STEPS * WAVES * 128];
+#pragma unroll
+        for (int r = 0; r < XR; ++r) {                       // float4 i holds floats 4 i .. 4 i + 3: step i / 32, lane slot (i % 32) / 2, half i % 2
+            const int i = tid + r * WAVES * 64;              // i < XR * 256 = STEPS * WAVES * 32: always inside xl
+            // unconditional: past K the clamped load's value lands in steps nobody reads (a store under `if` takes its load along into the branch: one full vmcnt wait per round)
+            *reinterpret_cast<u32x4*>(&xl[(i >> 5) * 128 + (i & 1) * 64 + ((i & 31) >> 1) * 4]) = xq[r];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) {
+            const bool ok = s0 + s < s1;
+            const int so = ok ? (s0 + s) : s0;
+            xa[s] = *reinterpret_cast<const float4*>(&xl[so * 128 + sub * 4]);
+            xb[s] = *reinterpret_cast<const float4*>(&xl[so * 128 + 64 + sub * 4]);
+            if (!ok) { xa[s] = make_float4(0.f, 0.f, 0.f, 0.f); xb[s] = xa[s]; }
+        }
+    } else if constexpr (NSP == 0) {
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) {
             const bool ok = s0 + s < s1;
@@ -187,7 +220,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_kernel(GemvArgs p) {
             if (!ok) { xa[s] = make_float4(0.f, 0.f, 0.f, 0.f); xb[s] = xa[s]; }
         }
     }
-    if (p.gamma) {                                           // fused Qwen2RMSNorm (host guarantees WAVES == 1 here)
+    if (!XLDS && p.gamma) {                                  // fused Qwen2RMSNorm (host guarantees WAVES == 1 here; never with XLDS: its 80 registers of gamma would come back)
         // gamma is requested BEFORE the reduction so its round trip overlaps the weight stream instead of following the shuffles
         float4 ga[STEPS], gb[STEPS];
 #pragma unroll
