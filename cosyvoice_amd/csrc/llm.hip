@@ -59,7 +59,7 @@ struct cv_llm {
     int fused_attn_oproj = 0, oproj_rblocks = 4, oproj_waves = 8; DevBuf opart, h2;
     int only_cat = -1;                  // cv_llm_profile_chain: enqueue only the launches of this category (-1 = all)
     DevBuf pf_x, pf_xn, pf_qkv, pf_attn, pf_gu, pf_act, pf_part; // prefill activations (grown on demand; pf_part: split-K partials of down on the weight-stationary path)
-    int prefill_rows = [] { const char* e = getenv("CV_PREFILL_ROWS"); return (e && e[0] == '1') ? 1 : 0; }();   // option "prefill_rows" = 1: prompts of <= 160 rows on skinny_rows_kernel (measured neutral: off)
+    int prefill_rows = [] { const char* e = getenv("CV_PREFILL_ROWS"); return (e && e[0] == '1') ? 1 : 0; }();   // option "prefill_rows" = 1: prompts of <= 160 rows on skinny_frag_kernel<0, ..> (measured neutral: off)
     int pf_rows = 0;
     // decode graph
     hipGraphExec_t graph = nullptr; hipStream_t graph_stream = nullptr; hipStream_t own_stream = nullptr;
@@ -74,7 +74,7 @@ struct cv_llm {
         int attn_mode = 1;                                       // with the fixed key partition): all kept - a batch crosses the rule's threshold as its contexts grow, a handle serves pinned and unpinned paths
         void drop_graphs() { for (auto& g : graphs) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; } }
     } bt;
-    // Round 3: fragment-ordered copies of the matrices for the batched decode (skinny_pk_kernel, llm_batch_kernels.h), made on the device the first time
+    // Round 3: fragment-ordered copies of the matrices for the batched decode (skinny_frag_kernel, llm_batch_kernels.h), made on the device the first time
     // the batch path is used: [row tile][k tile][lane][8 bf16], so that one wave load is 1 KB contiguous.  Keyed by the row-major tensor's address.
     // +0.73 GB of HBM for Qwen2-0.5B (the 288 GB of an MI355X are what the batched path is sized for).  Option "batch_packed" (default 1).
     // Shared between the handles that register the SAME weight tensors (a decode group's sibling handles, llm.py Qwen2LM.sibling): one copy per tensor address in a
@@ -200,8 +200,8 @@ static hipStream_t resolve(cv_llm* m, void* s) {
 
 static LinearW lw(const bf16_t* w, const float* b, int N, int K) { LinearW l; l.w = w; l.b = b; l.N = N; l.K = K; l.Kp = round_up32(K); l.bf16 = true; return l; }
 
-// Fragment-ordered copies of the matrices ([row tile][k tile][lane][8 bf16]: one wave load = 1 KB contiguous) for skinny_pk_kernel (batched decode) and
-// skinny_rows_kernel (prefill), made on the device once per handle, the first time either path runs.
+// Fragment-ordered copies of the matrices ([row tile][k tile][lane][8 bf16]: one wave load = 1 KB contiguous) for skinny_frag_kernel (batched decode,
+// prefill rows walk), made on the device once per handle, the first time either path runs.
 static void ensure_packed(cv_llm* m, hipStream_t s) {
     if (!m->batch_packed || !m->packed.empty()) return;
     const auto& c = m->cfg;
@@ -226,23 +226,53 @@ static void ensure_packed(cv_llm* m, hipStream_t s) {
     CV_HIP(hipGetLastError());
 }
 
-// the weight-stationary GEMM over the rows of a prefill (skinny_rows_kernel): geometry rules of skinny() for the fragment-ordered path
-static bool skinny_rows_fits(int N, int K, int ksplit) {
+// Skinny GEMMs of the batched decode and of the weight-stationary prefill (llm_batch_kernels.h): rt = row tiles (16 rows) per workgroup, ksplit = K ranges
+// across workgroups; the 32-wide k tiles of a range are split over the 4 waves of a workgroup, at most 7 each.  The fragment-ordered kernel stages every
+// wave's share of X through LDS, so every wave needs a tile: 4 .. 28 tiles per workgroup.
+static bool skinny_frag_fits(int K, int ksplit) {
     const int tiles = K / 32 / ksplit;
-    return K % (32 * ksplit) == 0 && tiles >= 4 && (tiles + 3) / 4 <= 7 && N % 4 == 0;
+    return K % (32 * ksplit) == 0 && tiles >= 4 && (tiles + 3) / 4 <= 7;
 }
-static void skinny_rows(const SkinnyArgs& a, int rt, hipStream_t s, const bf16_t* wp) {
+// the rows walk of a prefill exists on the fragment-ordered copies only and has no scalar tail for a ragged N
+static bool skinny_rows_fits(int N, int K, int ksplit) { return skinny_frag_fits(K, ksplit) && N % 4 == 0; }
+
+template <int CT>
+static void launch_skinny_frag(const SkinnyArgs& a, int rt, bool deep, dim3 grid, hipStream_t s) {
+    if (rt == 1) hipLaunchKernelGGL((skinny_frag_kernel<CT, 1, 7>), grid, dim3(256), 0, s, a);
+    else if (rt == 4) hipLaunchKernelGGL((skinny_frag_kernel<CT, 4, 7>), grid, dim3(256), 0, s, a);
+    else if (deep) hipLaunchKernelGGL((skinny_frag_kernel<CT, 2, 7>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((skinny_frag_kernel<CT, 2, 5>), grid, dim3(256), 0, s, a);
+}
+// wp = the fragment-ordered copy of a.W (ensure_packed), null: the row-major tensor.  rows = false: a decode step of a.nb <= 32 sequences; true: the a.nb rows of a prefill.
+static void skinny(const SkinnyArgs& a, int rt, hipStream_t s, const bf16_t* wp = nullptr, bool rows = false) {
     const int tiles = a.K / 32 / a.ksplit, row_tiles = (a.N + 15) / 16;
-    CV_CHECK(wp && skinny_rows_fits(a.N, a.K, a.ksplit), "skinny_rows: needs the fragment-ordered weights and a K range of 4 .. 28 tiles per workgroup");
-    CV_CHECK(!(a.gamma && a.ksplit != 1) && (a.mode == 2) == (a.ksplit > 1), "skinny_rows: split-K workgroups leave raw partials (mode 2), the fused norm needs the whole row");
-    SkinnyArgs b = a; b.W = wp;
+    const bool frag = wp && skinny_frag_fits(a.K, a.ksplit);       // same arithmetic, same bits as the row-major kernel, which also serves smaller K ranges
+    CV_CHECK(a.K % (32 * a.ksplit) == 0 && tiles >= 1 && (tiles + 3) / 4 <= 7 && (a.mode == 0 || a.N % 4 == 0), "skinny: K range must be a multiple of 32 and at most 28 tiles per workgroup");
+    CV_CHECK(!(a.gamma && a.ksplit != 1) && (a.mode == 2) == (a.ksplit > 1), "skinny: split-K workgroups leave raw partials (mode 2), the fused norm needs the whole row");
+    CV_CHECK(frag ? (rows ? a.N % 4 == 0 : a.nb <= MAX_NB) : !rows && a.nb <= 16,
+             "skinny: more than 16 rows need the fragment-ordered weight copies (K ranges of 4 .. 28 tiles per workgroup), more than 32 the rows walk (N a multiple of 4)");
     const dim3 grid(((row_tiles + rt - 1) / rt) * a.ksplit);
     const bool deep = (tiles + 3) / 4 > 5;
-    if (rt == 1) hipLaunchKernelGGL((skinny_rows_kernel<1, 7>), grid, dim3(256), 0, s, b);
-    else if (rt == 4) hipLaunchKernelGGL((skinny_rows_kernel<4, 7>), grid, dim3(256), 0, s, b);
-    else if (deep) hipLaunchKernelGGL((skinny_rows_kernel<2, 7>), grid, dim3(256), 0, s, b);
-    else hipLaunchKernelGGL((skinny_rows_kernel<2, 5>), grid, dim3(256), 0, s, b);
+    if (frag) {
+        SkinnyArgs b = a; b.W = wp;
+        if (rows) launch_skinny_frag<0>(b, rt, deep, grid, s);
+        else if (a.nb > 16) launch_skinny_frag<2>(b, rt, deep, grid, s);   // 17 .. 32 sequences: two MFMA column tiles per weight fragment
+        else launch_skinny_frag<1>(b, rt, deep, grid, s);
+        return;
+    }
+    // CV_SKINNY_X3=0: the products on the fp32 matrix pipe (8 v_mfma_f32_16x16x4_f32 per tile) instead of the exact three-term bf16 split (A/B knob)
+    static const bool x3 = [] { const char* e = getenv("CV_SKINNY_X3"); return !(e && e[0] == '0'); }();
+    if (x3) {
+        if (rt == 1) hipLaunchKernelGGL((skinny_mfma_kernel<1, 7, true>), grid, dim3(256), 0, s, a);
+        else if (deep) hipLaunchKernelGGL((skinny_mfma_kernel<2, 7, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((skinny_mfma_kernel<2, 5, true>), grid, dim3(256), 0, s, a);
+    } else {
+        if (rt == 1) hipLaunchKernelGGL((skinny_mfma_kernel<1, 7, false>), grid, dim3(256), 0, s, a);
+        else if (deep) hipLaunchKernelGGL((skinny_mfma_kernel<2, 7, false>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((skinny_mfma_kernel<2, 5, false>), grid, dim3(256), 0, s, a);
+    }
 }
+static void skinny_rows(const SkinnyArgs& a, int rt, hipStream_t s, const bf16_t* wp) { skinny(a, rt, s, wp, true); }
 static int down_ksplit(int inter);
 
 // One prompt segment of a prefill: rows [row0, row0 + L) of the stacked input are the positions pos0 .. pos0 + L - 1 of a sequence whose KV cache
@@ -261,7 +291,7 @@ static void llm_prefill_rows(cv_llm* m, const float* x_in, int R, const std::vec
     float* x = m->pf_x.as<float>(); float* xn = m->pf_xn.as<float>(); float* qkv = m->pf_qkv.as<float>();
     float* at = m->pf_attn.as<float>(); float* gu = m->pf_gu.as<float>(); float* act = m->pf_act.as<float>();
     CV_HIP(hipMemcpyAsync(x, x_in, (size_t)R * H * 4, hipMemcpyDeviceToDevice, s));
-    // Round 3, opt-in (prefill_rows): up to 160 rows (one prompt) the GEMMs run weight-stationary on the fragment-ordered copies (skinny_rows_kernel: RMSNorm
+    // Round 3, opt-in (prefill_rows): up to 160 rows (one prompt) the GEMMs run weight-stationary on the fragment-ordered copies (skinny_frag_kernel<0, ..>: RMSNorm
     // in the prologue, SiLU * up in the epilogue, split-K down + sum_partials) - 7 launches per layer instead of 9.  Measured 2.95 vs 2.99 ms: off by default.
     int dks = down_ksplit(c.inter);
     if (!skinny_rows_fits(H, c.inter, dks) && skinny_rows_fits(H, c.inter, 1)) dks = 1;       // small models: the whole K in one workgroup
@@ -597,46 +627,6 @@ static void batch_prefill_many(cv_llm* m, int n, const int32_t* slots, const flo
     CV_HIP(hipStreamSynchronize(s));
 }
 
-// skinny GEMM of the batched decode (llm_batch_kernels.h): rt = row tiles (16 rows) per workgroup, ksplit = K ranges across workgroups
-static void skinny(const SkinnyArgs& a, int rt, hipStream_t s, const bf16_t* wp = nullptr) {
-    const int tiles = a.K / 32 / a.ksplit, row_tiles = (a.N + 15) / 16;
-    if (wp && tiles >= 4 && (tiles + 3) / 4 <= 7) {          // fragment-ordered weights + wave-private activation staging (round 3); same arithmetic, same bits
-        CV_CHECK(a.K % (32 * a.ksplit) == 0 && (a.mode == 0 || a.N % 4 == 0), "skinny: K range must be a multiple of 32");
-        CV_CHECK(!(a.gamma && a.ksplit != 1) && (a.mode == 2) == (a.ksplit > 1), "skinny: split-K workgroups leave raw partials (mode 2), the fused norm needs the whole row");
-        SkinnyArgs b = a; b.W = wp;
-        const dim3 grid(((row_tiles + rt - 1) / rt) * a.ksplit);
-        const bool deep = (tiles + 3) / 4 > 5;
-        if (a.nb > 16) {                                       // 17 .. 32 sequences: two MFMA column tiles per weight fragment (skinny_pk2_kernel)
-            if (rt == 1) hipLaunchKernelGGL((skinny_pk2_kernel<1, 7>), grid, dim3(256), 0, s, b);
-            else if (rt == 4) { CV_CHECK(deep || tiles <= 28, "skinny: four row tiles per workgroup are for K ranges of up to 28 tiles"); hipLaunchKernelGGL((skinny_pk2_kernel<4, 7>), grid, dim3(256), 0, s, b); }
-            else if (deep) hipLaunchKernelGGL((skinny_pk2_kernel<2, 7>), grid, dim3(256), 0, s, b);
-            else hipLaunchKernelGGL((skinny_pk2_kernel<2, 5>), grid, dim3(256), 0, s, b);
-            return;
-        }
-        if (rt == 1) hipLaunchKernelGGL((skinny_pk_kernel<1, 7>), grid, dim3(256), 0, s, b);
-        else if (rt == 4) { CV_CHECK(deep || tiles <= 28, "skinny: four row tiles per workgroup are for K ranges of up to 28 tiles"); hipLaunchKernelGGL((skinny_pk_kernel<4, 7>), grid, dim3(256), 0, s, b); }
-        else if (deep) hipLaunchKernelGGL((skinny_pk_kernel<2, 7>), grid, dim3(256), 0, s, b);
-        else hipLaunchKernelGGL((skinny_pk_kernel<2, 5>), grid, dim3(256), 0, s, b);
-        return;
-    }
-    CV_CHECK(a.nb <= 16, "skinny: more than 16 sequences per step need the fragment-ordered weight copies (K ranges of 4 .. 28 tiles per workgroup)");
-    CV_CHECK(a.K % (32 * a.ksplit) == 0 && tiles >= 1 && (tiles + 3) / 4 <= 7 && (a.mode == 0 || a.N % 4 == 0), "skinny: K range must be a multiple of 32 and at most 28 tiles per workgroup");
-    CV_CHECK(!(a.gamma && a.ksplit != 1) && (a.mode == 2) == (a.ksplit > 1), "skinny: split-K workgroups leave raw partials (mode 2), the fused norm needs the whole row");
-    const dim3 grid(((row_tiles + rt - 1) / rt) * a.ksplit);
-    const bool deep = (tiles + 3) / 4 > 5;
-    // CV_SKINNY_X3=0: the products on the fp32 matrix pipe (8 v_mfma_f32_16x16x4_f32 per tile) instead of the exact three-term bf16 split (A/B knob)
-    static const bool x3 = [] { const char* e = getenv("CV_SKINNY_X3"); return !(e && e[0] == '0'); }();
-    if (x3) {
-        if (rt == 1) hipLaunchKernelGGL((skinny_mfma_kernel<1, 7, true>), grid, dim3(256), 0, s, a);
-        else if (deep) hipLaunchKernelGGL((skinny_mfma_kernel<2, 7, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((skinny_mfma_kernel<2, 5, true>), grid, dim3(256), 0, s, a);
-    } else {
-        if (rt == 1) hipLaunchKernelGGL((skinny_mfma_kernel<1, 7, false>), grid, dim3(256), 0, s, a);
-        else if (deep) hipLaunchKernelGGL((skinny_mfma_kernel<2, 7, false>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((skinny_mfma_kernel<2, 5, false>), grid, dim3(256), 0, s, a);
-    }
-}
-
 static void skinny_f8(const SkinnyF8Args& a, int rt, hipStream_t s) {
     const int tiles = a.K / 64 / a.ksplit, row_tiles = (a.N + 15) / 16;
     CV_CHECK(a.K % (64 * a.ksplit) == 0 && tiles >= 1 && (tiles + 3) / 4 <= 5 && (a.mode == 0 || a.N % 4 == 0), "skinny_f8: K range must be a multiple of 64 and at most 20 tiles per workgroup");
@@ -873,7 +863,7 @@ int cv_llm_set_option(cv_llm* m, const char* name, int32_t value) {
             CV_CHECK(value >= -1 && value <= 2, "batch_attn must be -1 (by slot count and context), 0 (VALU form), 1 (MFMA form) or 2 (MFMA form, one key partition for every slot count)");
             m->batch_attn = value;                               // (every form keeps its own captured step: no graph is dropped)
         }
-        else if (std::string(name) == "batch_packed") {      // batched decode on the fragment-ordered weight copies (skinny_pk_kernel) or on the row-major tensors (round 2)
+        else if (std::string(name) == "batch_packed") {      // batched decode on the fragment-ordered weight copies (skinny_frag_kernel) or on the row-major tensors (round 2)
             m->batch_packed = value != 0; m->bt.drop_graphs();
         }
         else if (std::string(name) == "batch_fp8") {         // batched decode on the fp8 copies of the weights (needs the .f8 / .f8s tensors)
@@ -983,6 +973,24 @@ int cv_skinny_fp8(const void* w8, const float* wscale, const float* bias, const 
     return guarded([&] {
         CV_CHECK(w8 && wscale && x && y && nb >= 1 && nb <= 16 && (rt == 1 || rt == 2), "cv_skinny_fp8: bad arguments");
         skinny_f8(SkinnyF8Args{reinterpret_cast<const unsigned char*>(w8), wscale, bias, x, ldx, y, ldy, N, K, gamma, eps, res, ldres, mode, nb, ksplit}, rt, as_stream(stream));
+    });
+}
+/* test hook: one bf16 skinny GEMM on caller-provided operands.  form 0: row-major W; 1 / 2: the batched decode / the prefill rows walk on a fragment-ordered copy made for the call */
+int cv_skinny(const void* w, const float* bias, const float* x, int64_t ldx, float* y, int64_t ldy, int32_t N, int32_t K, const float* gamma, float eps,
+              const float* res, int64_t ldres, int32_t mode, int32_t nb, int32_t ksplit, int32_t rt, int32_t form, void* stream) {
+    return guarded([&] {
+        CV_CHECK(w && x && y && N >= 1 && K >= 32 && ksplit >= 1 && nb >= 1 && form >= 0 && form <= 2 && (rt == 1 || rt == 2 || (rt == 4 && form != 0)), "cv_skinny: bad arguments");
+        hipStream_t s = as_stream(stream);
+        const SkinnyArgs a{static_cast<const bf16_t*>(w), bias, x, ldx, y, ldy, N, K, gamma, eps, res, ldres, mode, nb, ksplit};
+        if (form == 0) { skinny(a, rt, s); return; }
+        CV_CHECK(form == 2 ? skinny_rows_fits(N, K, ksplit) : skinny_frag_fits(K, ksplit) && nb <= MAX_NB, "cv_skinny: not a geometry of the fragment-ordered kernel");
+        const long long pieces = (long long)((N + 15) / 16) * (K / 32) * 64;
+        DevBuf wp; wp.ensure((size_t)pieces * 16);
+        bf16_t* packed = wp.as<bf16_t>();
+        hipLaunchKernelGGL(pack_frag_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, a.W, packed, (int)N, (int)K);
+        if (form == 1) skinny(a, rt, s, packed);
+        else skinny_rows(a, rt, s, packed);
+        CV_HIP(hipStreamSynchronize(s));                                   // wp is freed on return
     });
 }
 int cv_llm_batch_decode(cv_llm* m, int32_t n_steps, int32_t* out_tokens, int32_t* n_out, int32_t* finished, void* stream) {

@@ -25,7 +25,7 @@
 
 namespace cv {
 
-constexpr int MAX_NB = 32;        // lock-step slots: 16 per MFMA column tile, two column tiles per weight fragment (skinny_pk2_kernel)
+constexpr int MAX_NB = 32;        // lock-step slots: 16 per MFMA column tile, two column tiles per weight fragment (skinny_frag_kernel<2, ..>)
 
 struct SkinnyArgs {
     const bf16_t* W; const float* bias;
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_mfma_kernel(SkinnyArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Round 3: the same skinny GEMM with both operands fetched as WHOLE cache lines (skinny_pk_kernel).
+// The same skinny GEMM with both operands fetched as WHOLE cache lines (skinny_frag_kernel): the batched decode and the weight-stationary prefill.
 //
 // What bound skinny_mfma_kernel (tools/ubench/skinny_probe.hip, profiles/r3_skinny_probe.txt): not HBM - the launch takes as long with the weights
 // L2-warm - but the number of cache-line requests a CU's vector memory pipe has to walk.  With row-major operands a lane's fragment is 16 bytes of ITS
@@ -225,7 +225,25 @@ __global__ __launch_bounds__(NW * 64) void skinny_mfma_kernel(SkinnyArgs p) {
 //   * each wave fetches the activations of ITS k range row by row (one coalesced 16-byte-per-lane load per sequence: 896 B contiguous) into a wave-
 //     private LDS slab and reads its B fragments from there; gamma likewise.  No workgroup barrier is involved (a wave's DS operations execute in
 //     order; wave_lds_sync only pins the compiler), which is what made the round-2 LDS staging lose.
-// Same products in the same order as skinny_mfma_kernel<.., X3 = true>: bit-identical output (tests/test_zz_llm_batch.py runs both).
+// Same products in the same order as skinny_mfma_kernel<.., X3 = true>: bit-identical output (tests/test_skinny_kernels.py, tests/test_zz_llm_batch.py).
+//
+// The MFMA takes 16 rows of X (sequences of a decode step, rows of a prompt) as its B columns; the weight fragments a wave holds in registers are the
+// expensive operand (streamed from HBM once), so further GROUPS of 16 rows reuse them: group i + 1 is requested when group i has been parked in LDS (the
+// same 16 registers; the second group's loads queue behind the weight stream and land about when it does), multiplied against the same w[][] and combined /
+// stored by another pass of the epilogue.  Per row the products, their order and the cross-wave order do not depend on the group, on the row's slot
+// in it or on how many rows there are.  CT says how many groups a launch walks:
+//   CT = 1  up to 16 sequences of the batched decode: one group.  The only form with the clock stamps skinny_probe.hip reads.
+//   CT = 2  17 .. 32 sequences (32 lock-step slots): at most two groups, unrolled.
+//   CT = 0  any number of rows, a runtime loop: the prefill of one prompt (M = 131 rows for the benchmark utterance; option prefill_rows / CV_PREFILL_ROWS=1,
+//           off by default).  The tiled GEMM the prefill runs on (gemm_conv_kernel, AX3) restages a 32-row x 128-k tile seven times per output tile at
+//           M = 131: 22 us per launch for GEMMs whose weights a decode GEMV streams in 3-6 us; here a workgroup ingests its weight fragments once plus ALL rows
+//           of X over its k range (M x K x 4 B, from L2).  MEASURED on the MI355X (profiles/r3_prefill_rows_ab.txt): 2.95 ms per 131-row prefill against
+//           2.99 ms on the tiled GEMMs - the nine groups of a launch are a serial chain of LDS staging, MFMAs, cross-wave combine and two barriers (~2.4 us
+//           each), which is what the tiled kernel's seven k steps cost as well.  A second form (waves own different row tiles over the whole K, X shared
+//           through a double-buffered LDS tile, no cross-wave combine) measured 4.9-7.1 ms and was removed.
+//           Its weights are loaded with the default cache policy instead of non-temporal (the other row-group workgroups of the launch do not share them,
+//           but a second prompt's prefill right behind this one does), gamma is staged ahead of the loop, and there is no scalar tail: N % 4 == 0 (host check).
+// Modes / epilogues as SkinnyArgs (nb = number of rows).
 // ---------------------------------------------------------------------------------------------------------------------------------
 // W [N][K] row-major bf16 -> Wp [ceil(N / 16)][K / 32][64 lanes][8]: lane l = 16 g + c holds W[16 R + c][32 t + 8 g .. + 7] (rows >= N: zeros)
 static __global__ __launch_bounds__(256) void pack_frag_kernel(const bf16_t* W, bf16_t* Wp, int N, int K) {
@@ -241,8 +259,9 @@ static __global__ __launch_bounds__(256) void pack_frag_kernel(const bf16_t* W, 
     *reinterpret_cast<u32x4*>(Wp + i * 8) = v;
 }
 
-template <int RT, int KTW, int NW = 4>
-__global__ __launch_bounds__(NW * 64) CV_WAVES_PER_EU(1, 2) void skinny_pk_kernel(SkinnyArgs p) {          // p.W = the fragment-ordered copy
+template <int CT, int RT, int KTW, int NW = 4>
+__global__ __launch_bounds__(NW * 64) CV_WAVES_PER_EU(1, 2) void skinny_frag_kernel(SkinnyArgs p) {          // p.W = the fragment-ordered copy
+    static_assert(CT >= 0 && CT <= 2, "row groups per launch: one, at most two (unrolled), or a runtime count (0)");
     static_assert(RT >= 1 && RT <= 4 && RT <= NW && KTW <= 8, "one row tile per combining wave; a wave's k range is at most 256 columns (one 16-byte piece per lane)");
     constexpr int XP = KTW * 32 + 4;                                                  // floats per staged activation row (+4: rows start 16 bytes apart in the banks)
     __shared__ __attribute__((aligned(16))) float red[NW * RT * 256];
@@ -255,17 +274,18 @@ __global__ __launch_bounds__(NW * 64) CV_WAVES_PER_EU(1, 2) void skinny_pk_kerne
     const int t0 = wave * tiles / NW, t1 = (wave + 1) * tiles / NW, nt = t1 - t0;       // nt >= 1 (host check)
     const int kt0 = ks * tiles + t0;                                                  // first k tile of this wave in the whole K
     const int n_base = rg * RT * 16, row_tiles = (p.N + 15) / 16;
-    long long* dbg = p.dbg ? p.dbg + (long long)blockIdx.x * 8 : nullptr;
+    long long* dbg = CT == 1 && p.dbg ? p.dbg + (long long)blockIdx.x * 8 : nullptr;
     int dn = 0;
     auto stamp = [&]() { if (dbg && tid == 0) dbg[dn++] = clock64(); };
     stamp();
 
-    // ---- activations and gamma of the wave's k range FIRST (vmcnt retires in order: what is requested behind the weights waits for all of them)
+    // ---- activations (the first group) and gamma of the wave's k range FIRST (vmcnt retires in order: what is requested behind the weights waits for all of them)
     const int kx = kt0 * 32 + min(4 * lane, nt * 32 - 4);                             // lanes beyond the range re-read its last piece (not staged)
     // (16 named registers, not an array: with the scheduling fence below an array stays in scratch memory on this compiler)
-#define CV_XROW(b) const float4 xr##b = *reinterpret_cast<const float4*>(p.x + (long long)min(b, p.nb - 1) * p.ldx + kx);   /* rows >= nb repeat the last sequence (never stored) */
-    CV_XROW(0) CV_XROW(1) CV_XROW(2) CV_XROW(3) CV_XROW(4) CV_XROW(5) CV_XROW(6) CV_XROW(7) CV_XROW(8) CV_XROW(9) CV_XROW(10) CV_XROW(11) CV_XROW(12) CV_XROW(13) CV_XROW(14) CV_XROW(15)
-#undef CV_XROW
+    float4 xr0, xr1, xr2, xr3, xr4, xr5, xr6, xr7, xr8, xr9, xr10, xr11, xr12, xr13, xr14, xr15;
+#define CV_XROW(b) xr##b = *reinterpret_cast<const float4*>(p.x + (long long)min(gq * 16 + b, p.nb - 1) * p.ldx + kx);   /* rows >= nb repeat the last row (never stored) */
+#define CV_XLOAD_GROUP(G) { const int gq = (G); CV_XROW(0) CV_XROW(1) CV_XROW(2) CV_XROW(3) CV_XROW(4) CV_XROW(5) CV_XROW(6) CV_XROW(7) CV_XROW(8) CV_XROW(9) CV_XROW(10) CV_XROW(11) CV_XROW(12) CV_XROW(13) CV_XROW(14) CV_XROW(15) }
+    CV_XLOAD_GROUP(0)
     const float4 gr = *reinterpret_cast<const float4*>((p.gamma ? p.gamma : p.x) + kx);           // unconditional: a load in a branch splits the block the scheduler orders
     order_memory();                                                                   // keep these requests AHEAD of the weight stream (the scheduler would sink them behind it)
     // ---- the weight fragments: one contiguous run per row tile
@@ -278,153 +298,24 @@ __global__ __launch_bounds__(NW * 64) CV_WAVES_PER_EU(1, 2) void skinny_pk_kerne
         const bool ok = t < nt;
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-            u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wr[rt] + (ok ? t : 0) * 512));
+            const u32x4* src = reinterpret_cast<const u32x4*>(wr[rt] + (ok ? t : 0) * 512);
+            u32x4 v = CT == 0 ? *src : __builtin_nontemporal_load(src);
             if (!ok) v = (u32x4){0u, 0u, 0u, 0u};
             w[rt][t] = v;
         }
     }
-    // ---- stage the activations (the weights stay in flight)
-    if (4 * lane < nt * 32) {
-#define CV_XST(b) *reinterpret_cast<float4*>(&xs[wave][b * XP + 4 * lane]) = xr##b;
-        CV_XST(0) CV_XST(1) CV_XST(2) CV_XST(3) CV_XST(4) CV_XST(5) CV_XST(6) CV_XST(7) CV_XST(8) CV_XST(9) CV_XST(10) CV_XST(11) CV_XST(12) CV_XST(13) CV_XST(14) CV_XST(15)
-#undef CV_XST
-        *reinterpret_cast<float4*>(&gs[wave][4 * lane]) = gr;
-    }
-    wave_lds_sync();
+    if (CT == 0 && 4 * lane < nt * 32) *reinterpret_cast<float4*>(&gs[wave][4 * lane]) = gr;
 
-    float ss = 0.f;
-    v4f acc[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) acc[rt] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < KTW; ++t) {
-        if (t < nt) {                                                   // wave-uniform
-            float4 a4 = *reinterpret_cast<const float4*>(&xs[wave][c * XP + t * 32 + g * 8]);
-            float4 b4 = *reinterpret_cast<const float4*>(&xs[wave][c * XP + t * 32 + g * 8 + 4]);
-            if (p.gamma) {
-                const float4 ga = *reinterpret_cast<const float4*>(&gs[wave][t * 32 + g * 8]), gb = *reinterpret_cast<const float4*>(&gs[wave][t * 32 + g * 8 + 4]);
-                ss += a4.x * a4.x + a4.y * a4.y + a4.z * a4.z + a4.w * a4.w + b4.x * b4.x + b4.y * b4.y + b4.z * b4.z + b4.w * b4.w;
-                a4.x *= ga.x; a4.y *= ga.y; a4.z *= ga.z; a4.w *= ga.w;
-                b4.x *= gb.x; b4.y *= gb.y; b4.z *= gb.z; b4.w *= gb.w;
-            }
-            u32x4 h1, h2, h3;
-            split3_bf16(a4, b4, h1, h2, h3);
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {                           // smallest term first (as skinny_mfma_kernel)
-                const v8bf wf = __builtin_bit_cast(v8bf, w[rt][t]);
-                v4f a = acc[rt];
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(v8bf, h3), a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(v8bf, h2), a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(v8bf, h1), a, 0, 0, 0);
-                acc[rt] = a;
-            }
-            if (t == 0) stamp();
-        }
-    }
-    if (p.gamma) {
-        ss += __shfl_xor(ss, 16); ss += __shfl_xor(ss, 32);            // over the 4 k-slot groups of the wave
-        if (g == 0) ssq[wave][c] = ss;
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) *reinterpret_cast<float4*>(&red[((wave * RT + rt) * 64 + lane) * 4]) = make_float4(acc[rt][0], acc[rt][1], acc[rt][2], acc[rt][3]);
-    stamp();
-    __syncthreads();
-    stamp();
-    if (wave >= RT) return;
-    const int rt = wave;
-    float4 v = *reinterpret_cast<const float4*>(&red[(rt * 64 + lane) * 4]);
-#pragma unroll
-    for (int ww = 1; ww < NW; ++ww) {
-        const float4 o = *reinterpret_cast<const float4*>(&red[((ww * RT + rt) * 64 + lane) * 4]);
-        v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-    }
-    if (p.gamma) {
-        float tot = (ssq[0][c] + ssq[1][c]) + (ssq[2][c] + ssq[3][c]);
-        if constexpr (NW == 8) tot += (ssq[4][c] + ssq[5][c]) + (ssq[6][c] + ssq[7][c]);
-        const float rstd = rsqrtf(tot / (float)p.K + p.eps);
-        v.x *= rstd; v.y *= rstd; v.z *= rstd; v.w *= rstd;
-    }
-    const int n = n_base + rt * 16 + g * 4;
-    if (c >= p.nb || n >= p.N) return;
-    if (p.mode == 1) {
-        const float2 o = make_float2((v.x / (1.f + expf(-v.x))) * v.y, (v.z / (1.f + expf(-v.z))) * v.w);
-        *reinterpret_cast<float2*>(p.y + (long long)c * p.ldy + (n >> 1)) = o;
-    } else if (p.mode == 2) {
-        *reinterpret_cast<float4*>(p.y + ((long long)ks * p.nb + c) * p.ldy + n) = v;
-    } else if ((p.N & 3) == 0) {
-        if (p.bias) { const float4 b4 = *reinterpret_cast<const float4*>(p.bias + n); v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w; }
-        if (p.res) { const float4 r4 = *reinterpret_cast<const float4*>(p.res + (long long)c * p.ldres + n); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
-        *reinterpret_cast<float4*>(p.y + (long long)c * p.ldy + n) = v;
-    } else {
-        const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (n + i < p.N) {
-                float o = e[i];
-                if (p.bias) o += p.bias[n + i];
-                if (p.res) o += p.res[(long long)c * p.ldres + n + i];
-                p.y[(long long)c * p.ldy + n + i] = o;
-            }
-    }
-    stamp();
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// skinny_pk_kernel for 17 .. 32 sequences (round 4: 32 lock-step slots).  The MFMA takes 16 sequences as its B columns; the weight fragments a wave holds in
-// registers are the expensive operand (streamed from HBM once per step), so a second COLUMN TILE reuses them: sequences 16 .. 31 are requested when the first
-// sixteen have been parked in LDS (the same registers; their loads queue behind the weight stream and land about when it does), multiplied against the same
-// w[][] and combined / stored by a second pass of the epilogue.  Per sequence the products, their order and the cross-wave order are those of
-// skinny_pk_kernel: a sequence's result does not depend on its slot or on how many slots are in use (tests/test_zz_llm_batch.py).
-// ---------------------------------------------------------------------------------------------------------------------------------
-template <int RT, int KTW, int NW = 4>
-__global__ __launch_bounds__(NW * 64) CV_WAVES_PER_EU(1, 2) void skinny_pk2_kernel(SkinnyArgs p) {          // p.W = the fragment-ordered copy
-    static_assert(RT >= 1 && RT <= 4 && RT <= NW && KTW <= 8, "one row tile per combining wave; a wave's k range is at most 256 columns (one 16-byte piece per lane)");
-    constexpr int XP = KTW * 32 + 4;
-    __shared__ __attribute__((aligned(16))) float red[NW * RT * 256];
-    __shared__ float ssq[NW][16];
-    __shared__ __attribute__((aligned(16))) float xs[NW][16 * XP];
-    __shared__ __attribute__((aligned(16))) float gs[NW][KTW * 32];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-    const int ks = blockIdx.x % p.ksplit, rg = blockIdx.x / p.ksplit;
-    const int tilesK = p.K / 32, tiles = tilesK / p.ksplit;
-    const int t0 = wave * tiles / NW, t1 = (wave + 1) * tiles / NW, nt = t1 - t0;       // nt >= 1 (host check)
-    const int kt0 = ks * tiles + t0;
-    const int n_base = rg * RT * 16, row_tiles = (p.N + 15) / 16;
-
-    const int kx = kt0 * 32 + min(4 * lane, nt * 32 - 4);
-    float4 xr0, xr1, xr2, xr3, xr4, xr5, xr6, xr7, xr8, xr9, xr10, xr11, xr12, xr13, xr14, xr15;
-#define CV_XROW(b, base) xr##b = *reinterpret_cast<const float4*>(p.x + (long long)min((base) + b, p.nb - 1) * p.ldx + kx);   /* rows >= nb repeat the last sequence (never stored) */
-#define CV_XROWS(base) CV_XROW(0, base) CV_XROW(1, base) CV_XROW(2, base) CV_XROW(3, base) CV_XROW(4, base) CV_XROW(5, base) CV_XROW(6, base) CV_XROW(7, base) \
-                       CV_XROW(8, base) CV_XROW(9, base) CV_XROW(10, base) CV_XROW(11, base) CV_XROW(12, base) CV_XROW(13, base) CV_XROW(14, base) CV_XROW(15, base)
-    CV_XROWS(0)
-    const float4 gr = *reinterpret_cast<const float4*>((p.gamma ? p.gamma : p.x) + kx);
-    order_memory();                                                                   // keep these requests AHEAD of the weight stream
-    u32x4 w[RT][KTW];
-    const bf16_t* wr[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) wr[rt] = p.W + (((long long)min(rg * RT + rt, row_tiles - 1) * tilesK + kt0) * 64 + lane) * 8;
-#pragma unroll
-    for (int t = 0; t < KTW; ++t) {
-        const bool ok = t < nt;
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wr[rt] + (ok ? t : 0) * 512));
-            if (!ok) v = (u32x4){0u, 0u, 0u, 0u};
-            w[rt][t] = v;
-        }
-    }
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-        if (ct * 16 >= p.nb) break;                                                   // (uniform)
-        // ---- stage this column tile's activations (the weights stay in flight / in registers)
+    auto group = [&](const int grp) __attribute__((always_inline)) {
+        // ---- stage this group's activations (the weights stay in flight / in registers)
         if (4 * lane < nt * 32) {
 #define CV_XST(b) *reinterpret_cast<float4*>(&xs[wave][b * XP + 4 * lane]) = xr##b;
             CV_XST(0) CV_XST(1) CV_XST(2) CV_XST(3) CV_XST(4) CV_XST(5) CV_XST(6) CV_XST(7) CV_XST(8) CV_XST(9) CV_XST(10) CV_XST(11) CV_XST(12) CV_XST(13) CV_XST(14) CV_XST(15)
 #undef CV_XST
-            if (ct == 0) *reinterpret_cast<float4*>(&gs[wave][4 * lane]) = gr;
+            if (CT != 0 && grp == 0) *reinterpret_cast<float4*>(&gs[wave][4 * lane]) = gr;
         }
         wave_lds_sync();
-        if (ct == 0 && p.nb > 16) { CV_XROWS(16) }                                    // the second column tile: requested behind the weight stream, lands about when it does
+        if ((CT == 0 || grp + 1 < CT) && (grp + 1) * 16 < p.nb) CV_XLOAD_GROUP(grp + 1)   // the next group: in flight under this group's MFMAs, combine and stores
 
         float ss = 0.f;
         v4f acc[RT];
@@ -435,6 +326,7 @@ __global__ __launch_bounds__(NW * 64) CV_WAVES_PER_EU(1, 2) void skinny_pk2_kern
             if (t < nt) {                                                   // wave-uniform
                 float4 a4 = *reinterpret_cast<const float4*>(&xs[wave][c * XP + t * 32 + g * 8]);
                 float4 b4 = *reinterpret_cast<const float4*>(&xs[wave][c * XP + t * 32 + g * 8 + 4]);
+                // Fused Qwen2RMSNorm as in skinny_mfma_kernel: the MFMAs run on x * gamma, rstd is applied to the combined accumulators
                 if (p.gamma) {
                     const float4 ga = *reinterpret_cast<const float4*>(&gs[wave][t * 32 + g * 8]), gb = *reinterpret_cast<const float4*>(&gs[wave][t * 32 + g * 8 + 4]);
                     ss += a4.x * a4.x + a4.y * a4.y + a4.z * a4.z + a4.w * a4.w + b4.x * b4.x + b4.y * b4.y + b4.z * b4.z + b4.w * b4.w;
@@ -452,187 +344,69 @@ __global__ __launch_bounds__(NW * 64) CV_WAVES_PER_EU(1, 2) void skinny_pk2_kern
                     a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(v8bf, h1), a, 0, 0, 0);
                     acc[rt] = a;
                 }
+                if (t == 0) stamp();
             }
         }
         if (p.gamma) {
             ss += __shfl_xor(ss, 16); ss += __shfl_xor(ss, 32);            // over the 4 k-slot groups of the wave
             if (g == 0) ssq[wave][c] = ss;
         }
+        // split-K over the waves, combined in fixed order; wave rt finishes row tile rt  [waves][RT][64 lanes][4]
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) *reinterpret_cast<float4*>(&red[((wave * RT + rt) * 64 + lane) * 4]) = make_float4(acc[rt][0], acc[rt][1], acc[rt][2], acc[rt][3]);
+        stamp();
         __syncthreads();
+        stamp();
+        const int rt = wave, n = n_base + rt * 16 + g * 4, row = grp * 16 + c;          // 4 consecutive weight rows of row `row` of X
         if (wave < RT) {
-            const int rt = wave, seq = ct * 16 + c;
             float4 v = *reinterpret_cast<const float4*>(&red[(rt * 64 + lane) * 4]);
 #pragma unroll
             for (int ww = 1; ww < NW; ++ww) {
                 const float4 o = *reinterpret_cast<const float4*>(&red[((ww * RT + rt) * 64 + lane) * 4]);
                 v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
             }
-            if (p.gamma) {
+            if (p.gamma) {                                                  // statistics over the whole row: the waves' shares, fixed order
                 float tot = (ssq[0][c] + ssq[1][c]) + (ssq[2][c] + ssq[3][c]);
                 if constexpr (NW == 8) tot += (ssq[4][c] + ssq[5][c]) + (ssq[6][c] + ssq[7][c]);
                 const float rstd = rsqrtf(tot / (float)p.K + p.eps);
                 v.x *= rstd; v.y *= rstd; v.z *= rstd; v.w *= rstd;
             }
-            const int n = n_base + rt * 16 + g * 4;
-            if (seq < p.nb && n < p.N) {
-                if (p.mode == 1) {
+            if (row < p.nb && n < p.N) {
+                if (p.mode == 1) {                                          // (gate_j, up_j) row pairs -> two activations
                     const float2 o = make_float2((v.x / (1.f + expf(-v.x))) * v.y, (v.z / (1.f + expf(-v.z))) * v.w);
-                    *reinterpret_cast<float2*>(p.y + (long long)seq * p.ldy + (n >> 1)) = o;
+                    *reinterpret_cast<float2*>(p.y + (long long)row * p.ldy + (n >> 1)) = o;
                 } else if (p.mode == 2) {
-                    *reinterpret_cast<float4*>(p.y + ((long long)ks * p.nb + seq) * p.ldy + n) = v;
-                } else if ((p.N & 3) == 0) {
+                    *reinterpret_cast<float4*>(p.y + ((long long)ks * p.nb + row) * p.ldy + n) = v;
+                } else if (CT == 0 || (p.N & 3) == 0) {
                     if (p.bias) { const float4 b4 = *reinterpret_cast<const float4*>(p.bias + n); v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w; }
-                    if (p.res) { const float4 r4 = *reinterpret_cast<const float4*>(p.res + (long long)seq * p.ldres + n); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
-                    *reinterpret_cast<float4*>(p.y + (long long)seq * p.ldy + n) = v;
-                } else {
+                    if (p.res) { const float4 r4 = *reinterpret_cast<const float4*>(p.res + (long long)row * p.ldres + n); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
+                    *reinterpret_cast<float4*>(p.y + (long long)row * p.ldy + n) = v;
+                } else {                                                    // ragged N (the 6761-wide CosyVoice3 head): rows are not 16-byte aligned
                     const float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         if (n + i < p.N) {
                             float o = e[i];
                             if (p.bias) o += p.bias[n + i];
-                            if (p.res) o += p.res[(long long)seq * p.ldres + n + i];
-                            p.y[(long long)seq * p.ldy + n + i] = o;
+                            if (p.res) o += p.res[(long long)row * p.ldres + n + i];
+                            p.y[(long long)row * p.ldy + n + i] = o;
                         }
                 }
             }
         }
-        __syncthreads();                                                              // red / ssq / xs are reused by the second column tile
+        if (CT != 1) __syncthreads();                                       // red / ssq / xs are rewritten by the next group
+    };
+    if constexpr (CT == 0) {
+        for (int grp = 0; grp * 16 < p.nb; ++grp) group(grp);
+    } else {
+#pragma unroll
+        for (int grp = 0; grp < CT; ++grp)
+            if (grp == 0 || grp * 16 < p.nb) group(grp);                     // (uniform)
     }
-#undef CV_XROWS
-#undef CV_XROW
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// The same weight-stationary GEMM over MANY rows (round 3: the prefill of one prompt, M = 131 rows for the benchmark utterance).
-// The tiled GEMM the prefill ran on (gemm_conv_kernel, AX3) restages a 32-row x 128-k tile seven times per output tile at M = 131: 22 us per
-// launch for GEMMs whose weights a decode GEMV streams in 3-6 us.  Here a workgroup is what it is in skinny_pk_kernel - RT row tiles of the
-// fragment-ordered weights, requested ONCE and kept in registers - and walks the rows of X in groups of 16 (the MFMA's B columns): group i + 1
-// is requested while group i is multiplied, combined and stored.  What a workgroup ingests is its weight fragments plus ALL rows of X over its
-// k range (M x K x 4 B, from L2); per output element the arithmetic (three-term split, k order, cross-wave order) is exactly the batched
-// decode's, so a row's result does not depend on M or on its position.  Modes / epilogues as SkinnyArgs (nb = number of rows).
-// MEASURED on the MI355X (profiles/r3_prefill_rows_ab.txt): 2.95 ms per 131-row prefill against 2.99 ms on the tiled GEMMs - the nine groups of a launch are a
-// serial chain of LDS staging, MFMAs, cross-wave combine and two barriers (~2.4 us each), which is what the tiled kernel's seven k steps cost as well.  A second
-// form (waves own different row tiles over the whole K, X shared through a double-buffered LDS tile, no cross-wave combine) measured 4.9-7.1 ms and was removed.
-// Opt-in (option prefill_rows / CV_PREFILL_ROWS=1); the tiled path stays the default.
-// ---------------------------------------------------------------------------------------------------------------------------------
-template <int RT, int KTW, int NW = 4>
-__global__ __launch_bounds__(NW * 64) CV_WAVES_PER_EU(1, 2) void skinny_rows_kernel(SkinnyArgs p) {          // p.W = the fragment-ordered copy
-    static_assert(RT >= 1 && RT <= 4 && RT <= NW && KTW <= 8, "one row tile per combining wave; a wave's k range is at most 256 columns (one 16-byte piece per lane)");
-    constexpr int XP = KTW * 32 + 4;
-    __shared__ __attribute__((aligned(16))) float red[NW * RT * 256];
-    __shared__ float ssq[NW][16];
-    __shared__ __attribute__((aligned(16))) float xs[NW][16 * XP];
-    __shared__ __attribute__((aligned(16))) float gs[NW][KTW * 32];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-    const int ks = blockIdx.x % p.ksplit, rg = blockIdx.x / p.ksplit;
-    const int tilesK = p.K / 32, tiles = tilesK / p.ksplit;
-    const int t0 = wave * tiles / NW, t1 = (wave + 1) * tiles / NW, nt = t1 - t0;       // nt >= 1 (host check)
-    const int kt0 = ks * tiles + t0;
-    const int n_base = rg * RT * 16, row_tiles = (p.N + 15) / 16;
-    const int ngroups = (p.nb + 15) / 16;
-    const int kx = kt0 * 32 + min(4 * lane, nt * 32 - 4);
-    // (16 named registers, not an array: next to the scheduling fence an array stays in scratch memory on this compiler - as in skinny_pk_kernel)
-    float4 xr0, xr1, xr2, xr3, xr4, xr5, xr6, xr7, xr8, xr9, xr10, xr11, xr12, xr13, xr14, xr15;
-#define CV_XROW(b) xr##b = *reinterpret_cast<const float4*>(p.x + (long long)min(gq * 16 + b, p.nb - 1) * p.ldx + kx);   /* rows >= nb repeat the last row (never stored) */
-#define CV_XLOAD_GROUP(G) { const int gq = (G); CV_XROW(0) CV_XROW(1) CV_XROW(2) CV_XROW(3) CV_XROW(4) CV_XROW(5) CV_XROW(6) CV_XROW(7) CV_XROW(8) CV_XROW(9) CV_XROW(10) CV_XROW(11) CV_XROW(12) CV_XROW(13) CV_XROW(14) CV_XROW(15) }
-    CV_XLOAD_GROUP(0)
-    const float4 gr = *reinterpret_cast<const float4*>((p.gamma ? p.gamma : p.x) + kx);
-    order_memory();                                                                   // the first group and gamma AHEAD of the weight stream
-    u32x4 w[RT][KTW];
-    const bf16_t* wr[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) wr[rt] = p.W + (((long long)min(rg * RT + rt, row_tiles - 1) * tilesK + kt0) * 64 + lane) * 8;
-#pragma unroll
-    for (int t = 0; t < KTW; ++t) {
-        const bool ok = t < nt;
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            u32x4 v = *reinterpret_cast<const u32x4*>(wr[rt] + (ok ? t : 0) * 512);   // default cache policy: the other row-group workgroups of the launch do not share these, but a
-            if (!ok) v = (u32x4){0u, 0u, 0u, 0u};                                     // second prompt's prefill right behind this one does
-            w[rt][t] = v;
-        }
-    }
-    if (4 * lane < nt * 32) *reinterpret_cast<float4*>(&gs[wave][4 * lane]) = gr;
-    for (int grp = 0; grp < ngroups; ++grp) {
-        if (4 * lane < nt * 32) {
-#define CV_XST(b) *reinterpret_cast<float4*>(&xs[wave][b * XP + 4 * lane]) = xr##b;
-            CV_XST(0) CV_XST(1) CV_XST(2) CV_XST(3) CV_XST(4) CV_XST(5) CV_XST(6) CV_XST(7) CV_XST(8) CV_XST(9) CV_XST(10) CV_XST(11) CV_XST(12) CV_XST(13) CV_XST(14) CV_XST(15)
-#undef CV_XST
-        }
-        wave_lds_sync();
-        if (grp + 1 < ngroups) CV_XLOAD_GROUP(grp + 1)                    // in flight under this group's MFMAs, combine and stores
-        float ss = 0.f;
-        v4f acc[RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < KTW; ++t) {
-            if (t < nt) {                                                   // wave-uniform
-                float4 a4 = *reinterpret_cast<const float4*>(&xs[wave][c * XP + t * 32 + g * 8]);
-                float4 b4 = *reinterpret_cast<const float4*>(&xs[wave][c * XP + t * 32 + g * 8 + 4]);
-                if (p.gamma) {
-                    const float4 ga = *reinterpret_cast<const float4*>(&gs[wave][t * 32 + g * 8]), gb = *reinterpret_cast<const float4*>(&gs[wave][t * 32 + g * 8 + 4]);
-                    ss += a4.x * a4.x + a4.y * a4.y + a4.z * a4.z + a4.w * a4.w + b4.x * b4.x + b4.y * b4.y + b4.z * b4.z + b4.w * b4.w;
-                    a4.x *= ga.x; a4.y *= ga.y; a4.z *= ga.z; a4.w *= ga.w;
-                    b4.x *= gb.x; b4.y *= gb.y; b4.z *= gb.z; b4.w *= gb.w;
-                }
-                u32x4 h1, h2, h3;
-                split3_bf16(a4, b4, h1, h2, h3);
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {                           // smallest term first (as skinny_mfma_kernel)
-                    const v8bf wf = __builtin_bit_cast(v8bf, w[rt][t]);
-                    v4f a = acc[rt];
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(v8bf, h3), a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(v8bf, h2), a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(v8bf, h1), a, 0, 0, 0);
-                    acc[rt] = a;
-                }
-            }
-        }
-        if (p.gamma) {
-            ss += __shfl_xor(ss, 16); ss += __shfl_xor(ss, 32);
-            if (g == 0) ssq[wave][c] = ss;
-        }
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) *reinterpret_cast<float4*>(&red[((wave * RT + rt) * 64 + lane) * 4]) = make_float4(acc[rt][0], acc[rt][1], acc[rt][2], acc[rt][3]);
-        __syncthreads();
-        if (wave < RT) {
-            const int rt = wave;
-            float4 v = *reinterpret_cast<const float4*>(&red[(rt * 64 + lane) * 4]);
-#pragma unroll
-            for (int ww = 1; ww < NW; ++ww) {
-                const float4 o = *reinterpret_cast<const float4*>(&red[((ww * RT + rt) * 64 + lane) * 4]);
-                v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-            }
-            if (p.gamma) {
-                const float tot = (ssq[0][c] + ssq[1][c]) + (ssq[2][c] + ssq[3][c]);
-                const float rstd = rsqrtf(tot / (float)p.K + p.eps);
-                v.x *= rstd; v.y *= rstd; v.z *= rstd; v.w *= rstd;
-            }
-            const int n = n_base + rt * 16 + g * 4;
-            const int row = grp * 16 + c;
-            if (row < p.nb && n < p.N) {
-                if (p.mode == 1) {
-                    const float2 o = make_float2((v.x / (1.f + expf(-v.x))) * v.y, (v.z / (1.f + expf(-v.z))) * v.w);
-                    *reinterpret_cast<float2*>(p.y + (long long)row * p.ldy + (n >> 1)) = o;
-                } else if (p.mode == 2) {
-                    *reinterpret_cast<float4*>(p.y + ((long long)ks * p.nb + row) * p.ldy + n) = v;
-                } else {                                                    // N % 4 == 0 (host check)
-                    if (p.bias) { const float4 b4 = *reinterpret_cast<const float4*>(p.bias + n); v.x += b4.x; v.y += b4.y; v.z += b4.z; v.w += b4.w; }
-                    if (p.res) { const float4 r4 = *reinterpret_cast<const float4*>(p.res + (long long)row * p.ldres + n); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
-                    *reinterpret_cast<float4*>(p.y + (long long)row * p.ldy + n) = v;
-                }
-            }
-        }
-        __syncthreads();                                                     // red / ssq are rewritten by the next group
-    }
-}
-
+    stamp();
 #undef CV_XLOAD_GROUP
 #undef CV_XROW
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // fp8 variant of the skinny GEMM (BASELINE.json configs[4]: "fp8 MFMA LLM path"; opt-in, batched decode only).  Weights: OCP e4m3 with one fp32

@@ -171,6 +171,12 @@ int cv_llm_batch_decode(cv_llm* m, int32_t n_steps, int32_t* out_tokens, int32_t
  * [ksplit][nb][N]; rt = row tiles (16 rows) per workgroup. */
 int cv_skinny_fp8(const void* w8, const float* wscale, const float* bias, const float* x, int64_t ldx, float* y, int64_t ldy, int32_t N, int32_t K,
                   const float* gamma, float eps, const float* res, int64_t ldres, int32_t mode, int32_t nb, int32_t ksplit, int32_t rt, void* stream);
+/* Test hook of the bf16 skinny GEMMs behind the batched decode and the weight-stationary prefill: arguments as cv_skinny_fp8 with W [N][K] row-major
+ * bf16.  form 0: the kernel on the row-major tensor (nb <= 16, rt 1 or 2); form 1: the batched decode on a fragment-ordered copy (nb <= 32);
+ * form 2: the prefill's walk over any number of rows on a fragment-ordered copy.  Forms 1 and 2 pack W into a buffer that lives for the call and
+ * go through the host function the model uses; a geometry the fragment-ordered kernel does not serve is an error, not a launch. */
+int cv_skinny(const void* w, const float* bias, const float* x, int64_t ldx, float* y, int64_t ldy, int32_t N, int32_t K, const float* gamma, float eps,
+              const float* res, int64_t ldres, int32_t mode, int32_t nb, int32_t ksplit, int32_t rt, int32_t form, void* stream);
 int cv_llm_last_logits(cv_llm* m, float* host_out, void* stream);
 int cv_llm_batch_logits(cv_llm* m, int32_t slot, float* host_out, void* stream);      /* test hook: one slot's logits after the last batched step */
 int cv_llm_last_hidden(cv_llm* m, float* host_out, void* stream);

@@ -231,7 +231,7 @@ def test_fused_qkv_attention_variant(lib, tiny_sd, splits, n_prompt):
 
 @pytest.mark.parametrize("n_prompt", [9, 120])
 def test_prefill_weight_stationary_rows_path(lib, tiny_sd, n_prompt):
-    """Round 3, option prefill_rows = 1: prompts of up to 160 rows run their GEMMs weight-stationary on the fragment-ordered copies (skinny_rows_kernel:
+    """Round 3, option prefill_rows = 1: prompts of up to 160 rows run their GEMMs weight-stationary on the fragment-ordered copies (skinny_frag_kernel<0, ..>:
     RMSNorm in the prologue, SiLU * up in the epilogue, rows of X walked in groups of 16 - two groups with a ragged last one, nine groups) instead of the
     tiled GEMMs (the default; measured equally fast on the MI355X).  Both give the oracle's first-step log-probabilities and greedy tokens, and the K / V
     they leave serve the same decode."""

@@ -57,7 +57,7 @@ def test_deep_down_projection_variant(lib, monkeypatch):
 
 def test_row_major_skinny_variant(lib):
     """Option batch_packed = 0: the batched GEMMs on the row-major weight tensors (skinny_mfma_kernel, round 2) instead of the fragment-ordered copies +
-    wave-private activation staging (skinny_pk_kernel, round 3, the default).  Same products in the same order: the same tokens, and the oracle's."""
+    wave-private activation staging (skinny_frag_kernel, round 3, the default).  Same products in the same order: the same tokens, and the oracle's."""
     import ctypes as C
     cfg = W.tiny()[0]
     sd = W.make_llm(cfg)
@@ -87,7 +87,7 @@ def test_batch_of_eight_and_long_context(lib):
 
 @pytest.mark.parametrize("nb", [17, 32])
 def test_more_than_sixteen_slots(lib, nb):
-    """Round 4: 17 .. 32 sequences per lock-step step - a second MFMA column tile per weight fragment (skinny_pk2_kernel): every slot still yields exactly the
+    """Round 4: 17 .. 32 sequences per lock-step step - a second MFMA column tile per weight fragment (skinny_frag_kernel<2, ..>): every slot still yields exactly the
     tokens of its request alone (= the oracle's), whatever its column tile, with different prompt lengths and early stops; then a smaller batch and a
     continuous-batching queue over 20 slots on the same handle."""
     cfg = W.tiny()[0]

@@ -1,4 +1,4 @@
-"""Dev probe (round 3): LLM prefill of the U10 prompt (131 rows) on the weight-stationary rows path (skinny_rows_kernel, option prefill_rows = 1) against the tiled
+"""Dev probe (round 3): LLM prefill of the U10 prompt (131 rows) on the weight-stationary rows path (skinny_frag_kernel<0, ..>, option prefill_rows = 1) against the tiled
 GEMMs of round 2 (prefill_rows = 0): ms per prefill (best of 10, one synchronisation each), then the 250 greedy tokens of both against the committed oracle
 tokens.   gpurun -- python tools/probe_prefill_rows.py"""
 import sys, time, os, json, ctypes as C

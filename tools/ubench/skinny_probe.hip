@@ -134,45 +134,45 @@ int main() {
         us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_mfma_kernel<2, 5, true>), g_down, dim3(256), 0, s, down(l)); });
         printf("down     skinny<2,5> 8 K ranges (8.7 MB, %3u WG)             %6.2f us per launch\n", g_down.x, us);
         stamps("down split-K", skinny_mfma_kernel<2, 5, true>, g_down, down(3), dbg);
-        // ---- round 3: fragment-ordered weights + wave-private activation staging (skinny_pk_kernel)
+        // ---- round 3: fragment-ordered weights + wave-private activation staging (skinny_frag_kernel, one group of up to 16 sequences)
         auto with = [&](SkinnyArgs a, const bf16_t* wp, float* out) { a.W = wp; a.y = out; return a; };
         (void)hipMemset(y, 0, (size_t)16 * 2 * I * 4); (void)hipMemset(y2, 0, (size_t)16 * 2 * I * 4);
-        hipLaunchKernelGGL((skinny_mfma_kernel<2, 7, true>), g_gu, dim3(256), 0, nullptr, gu(3, gam)); hipLaunchKernelGGL((skinny_pk_kernel<2, 7>), g_gu, dim3(256), 0, nullptr, with(gu(3, gam), pgu[3], y2));
+        hipLaunchKernelGGL((skinny_mfma_kernel<2, 7, true>), g_gu, dim3(256), 0, nullptr, gu(3, gam)); hipLaunchKernelGGL((skinny_frag_kernel<1, 2, 7>), g_gu, dim3(256), 0, nullptr, with(gu(3, gam), pgu[3], y2));
         const size_t bad_gu = same((size_t)nb * I);
-        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_pk_kernel<2, 7>), g_gu, dim3(256), 0, s, with(gu(l, gam), pgu[l], y2)); });
-        printf("gate/up  skinny_pk<2,7> + RMSNorm                            %6.2f us per launch   (%zu values differ from skinny_mfma)\n", us, bad_gu);
-        stamps("pk gate/up + norm", skinny_pk_kernel<2, 7>, g_gu, with(gu(3, gam), pgu[3], y2), dbg);
-        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_pk_kernel<4, 7>), dim3((2 * I / 16 + 3) / 4), dim3(256), 0, s, with(gu(l, gam), pgu[l], y2)); });
-        printf("gate/up  skinny_pk<4,7> + RMSNorm (152 WG)                   %6.2f us per launch\n", us);
-        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_pk_kernel<1, 7>), dim3(2 * I / 16), dim3(256), 0, s, with(gu(l, gam), pgu[l], y2)); });
-        printf("gate/up  skinny_pk<1,7> + RMSNorm (608 WG)                   %6.2f us per launch\n", us);
+        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_frag_kernel<1, 2, 7>), g_gu, dim3(256), 0, s, with(gu(l, gam), pgu[l], y2)); });
+        printf("gate/up  skinny_frag<1,2,7> + RMSNorm                            %6.2f us per launch   (%zu values differ from skinny_mfma)\n", us, bad_gu);
+        stamps("frag gate/up + norm", skinny_frag_kernel<1, 2, 7>, g_gu, with(gu(3, gam), pgu[3], y2), dbg);
+        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_frag_kernel<1, 4, 7>), dim3((2 * I / 16 + 3) / 4), dim3(256), 0, s, with(gu(l, gam), pgu[l], y2)); });
+        printf("gate/up  skinny_frag<1,4,7> + RMSNorm (152 WG)                   %6.2f us per launch\n", us);
+        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_frag_kernel<1, 1, 7>), dim3(2 * I / 16), dim3(256), 0, s, with(gu(l, gam), pgu[l], y2)); });
+        printf("gate/up  skinny_frag<1,1,7> + RMSNorm (608 WG)                   %6.2f us per launch\n", us);
         (void)hipMemset(y, 0, (size_t)16 * Q * 4); (void)hipMemset(y2, 0, (size_t)16 * Q * 4);
-        hipLaunchKernelGGL((skinny_mfma_kernel<1, 7, true>), g_qkv, dim3(256), 0, nullptr, qkv(3, gam)); hipLaunchKernelGGL((skinny_pk_kernel<1, 7>), g_qkv, dim3(256), 0, nullptr, with(qkv(3, gam), pqkv[3], y2));
+        hipLaunchKernelGGL((skinny_mfma_kernel<1, 7, true>), g_qkv, dim3(256), 0, nullptr, qkv(3, gam)); hipLaunchKernelGGL((skinny_frag_kernel<1, 1, 7>), g_qkv, dim3(256), 0, nullptr, with(qkv(3, gam), pqkv[3], y2));
         const size_t bad_qkv = same((size_t)nb * Q);
-        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_pk_kernel<1, 7>), g_qkv, dim3(256), 0, s, with(qkv(l, gam), pqkv[l], y2)); });
-        printf("qkv      skinny_pk<1,7> + RMSNorm                            %6.2f us per launch   (%zu values differ)\n", us, bad_qkv);
-        stamps("pk qkv + norm", skinny_pk_kernel<1, 7>, g_qkv, with(qkv(3, gam), pqkv[3], y2), dbg);
+        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_frag_kernel<1, 1, 7>), g_qkv, dim3(256), 0, s, with(qkv(l, gam), pqkv[l], y2)); });
+        printf("qkv      skinny_frag<1,1,7> + RMSNorm                            %6.2f us per launch   (%zu values differ)\n", us, bad_qkv);
+        stamps("frag qkv + norm", skinny_frag_kernel<1, 1, 7>, g_qkv, with(qkv(3, gam), pqkv[3], y2), dbg);
         (void)hipMemset(y, 0, (size_t)16 * H * 4); (void)hipMemset(y2, 0, (size_t)16 * H * 4);
-        hipLaunchKernelGGL((skinny_mfma_kernel<1, 7, true>), g_o, dim3(256), 0, nullptr, op(3)); hipLaunchKernelGGL((skinny_pk_kernel<1, 7>), g_o, dim3(256), 0, nullptr, with(op(3), po[3], y2));
+        hipLaunchKernelGGL((skinny_mfma_kernel<1, 7, true>), g_o, dim3(256), 0, nullptr, op(3)); hipLaunchKernelGGL((skinny_frag_kernel<1, 1, 7>), g_o, dim3(256), 0, nullptr, with(op(3), po[3], y2));
         const size_t bad_o = same((size_t)nb * H);
-        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_pk_kernel<1, 7>), g_o, dim3(256), 0, s, with(op(l), po[l], y2)); });
-        printf("o_proj   skinny_pk<1,7> + residual                           %6.2f us per launch   (%zu values differ)\n", us, bad_o);
+        us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_frag_kernel<1, 1, 7>), g_o, dim3(256), 0, s, with(op(l), po[l], y2)); });
+        printf("o_proj   skinny_frag<1,1,7> + residual                           %6.2f us per launch   (%zu values differ)\n", us, bad_o);
         {
             auto dn = [&](int l, float* out) { SkinnyArgs a = down(l); a.W = pdown[l]; a.y = out; return a; };
             float* dp2 = y2;
             (void)hipMemset(dpart, 0, (size_t)8 * 16 * H * 4); (void)hipMemset(dp2, 0, (size_t)8 * 16 * H * 4);
-            hipLaunchKernelGGL((skinny_mfma_kernel<2, 5, true>), g_down, dim3(256), 0, nullptr, down(3)); hipLaunchKernelGGL((skinny_pk_kernel<2, 5>), g_down, dim3(256), 0, nullptr, dn(3, dp2));
+            hipLaunchKernelGGL((skinny_mfma_kernel<2, 5, true>), g_down, dim3(256), 0, nullptr, down(3)); hipLaunchKernelGGL((skinny_frag_kernel<1, 2, 5>), g_down, dim3(256), 0, nullptr, dn(3, dp2));
             (void)hipDeviceSynchronize();
             std::vector<float> a((size_t)8 * nb * H), b(a.size());
             (void)hipMemcpy(a.data(), dpart, a.size() * 4, hipMemcpyDeviceToHost); (void)hipMemcpy(b.data(), dp2, b.size() * 4, hipMemcpyDeviceToHost);
             size_t bad = 0; for (size_t i = 0; i < a.size(); ++i) bad += memcmp(&a[i], &b[i], 4) != 0;
-            us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_pk_kernel<2, 5>), g_down, dim3(256), 0, s, dn(l, dp2)); });
-            printf("down     skinny_pk<2,5> 8 K ranges                           %6.2f us per launch   (%zu values differ)\n", us, bad);
-            stamps("pk down split-K", skinny_pk_kernel<2, 5>, g_down, dn(3, dp2), dbg);
+            us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_frag_kernel<1, 2, 5>), g_down, dim3(256), 0, s, dn(l, dp2)); });
+            printf("down     skinny_frag<1,2,5> 8 K ranges                           %6.2f us per launch   (%zu values differ)\n", us, bad);
+            stamps("frag down split-K", skinny_frag_kernel<1, 2, 5>, g_down, dn(3, dp2), dbg);
             // 4 K ranges x 1 row tile: 56 x 4 = 224 workgroups as well, half the partial sums
             auto dn4 = [&](int l) { SkinnyArgs a = down(l); a.W = pdown[l]; a.y = dp2; a.ksplit = 4; return a; };
-            us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_pk_kernel<1, 8, 5>), dim3(56 * 4), dim3(320), 0, s, dn4(l)); });
-            printf("down     skinny_pk<1,8,5 waves> 4 K ranges x 1 row tile      %6.2f us per launch\n", us);
+            us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL((skinny_frag_kernel<1, 1, 8, 5>), dim3(56 * 4), dim3(320), 0, s, dn4(l)); });
+            printf("down     skinny_frag<1,1,8,5 waves> 4 K ranges x 1 row tile      %6.2f us per launch\n", us);
         }
         us = time_graph(NL, [&](hipStream_t s) { for (int l = 0; l < NL; ++l) hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((nb * H / 4 + 255) / 256)), dim3(256), 0, s, dpart, 8, nb, H, res, (long long)H, res, (long long)H); });
         printf("sum_partials_kernel                                          %6.2f us per launch\n", us);
