@@ -39,6 +39,7 @@ struct Lm1Dyn {
 
 enum { LM1_PRO_NONE = 0, LM1_PRO_LN = 1, LM1_PRO_MERGE = 2 };
 
+constexpr int LM1_MAX_SLOTS = 8;               // sequences of the lock-step batched decode (cv_lm1_batch_*)
 struct Lm1GemvArgs {
     const float* x;                            // [K] (NONE / LN) or the attention partials [heads][LM1_SPLITS][66] (MERGE)
     const float* g; const float* b; float eps; // LN prologue
@@ -47,6 +48,9 @@ struct Lm1GemvArgs {
     int set_pos;                               // >= 0: block 0 publishes the step's position (first kernel of a step); -2: the position of the device loop (st->pos)
     const DecodeState* st;                     // set_pos == -2 (cv_lm1_decode): the loop state the sampler and advance_pos_kernel keep on the device
     int N, K, Kp, act, pro;
+    // the slots of the batched decode: x / res / y above are slot 0's, dyn / st are [nb] (Lm1Dyn::pad0 != 0: the slot takes part in the step); the matrix, bias, gamma / beta are shared
+    long long sx, sres, sy;                    // floats between two slots' x / res / y
+    int nb;                                    // 0: the single sequence
 };
 
 // The prologue of the decode GEMVs: the input vector into LDS (xs, zero beyond K up to steps * 64 floats), by one of three rules; `issue_weights()` requests the caller's
@@ -157,321 +161,186 @@ static __device__ __forceinline__ void lm1_gemv_prologue(const Lm1GemvArgs& p, f
     }
 }
 
-// y[N] = act(pro(x)[K] . W[N][K]^T + bias) (+ res).  4 output rows per workgroup, a 16-lane group per row, the 4 waves split K (gemv_f32_kernel).
-// U: 64-float steps a lane group has in flight (a wave's share of K = 1024 is 4 steps).  The wave's FIRST group of weight loads is issued before the prologue:
-// the weights do not depend on the previous kernel's output, the input vector does, so the prologue's dependent loads (x, gamma, beta) wait under them.
-// NW: waves per workgroup (they split K): 4, or 8 for the K = 4096 product whose 1024 rows are only 256 workgroups - 16 steps per wave were two dependent
-// round trips per wave, 8 steps are one.
-// W16 (round 6, the model's fp16 mode: cv_lm1_use_bf16): the matrix is stored as bf16 [N][Kp]; a lane takes the SAME four k-values of a step as 8 bytes and widens them when
-// the step is consumed - the products and their order are those of the fp32 kernel on the bf16-rounded weights, half the bytes per token.
+// ---- the decode GEMVs: y[N] = act(pro(x)[K] . W[N][K]^T + bias) (+ res), for the single sequence (NBT = 0) or for NBT = 1 / 2 / 4 / 8 slots of the lock-step batch -------
+// Two kernels, each ONE body for both: a lane owns a (row, k-subset) and carries one accumulator per slot, so for every slot the products, their order, the 16-lane
+// reduction and the combine of the waves' partial sums are those of the single sequence - a slot's output has the bits of cv_lm1_step on that sequence alone, whatever
+// the slot count and whichever slot it sits in, and every weight row is read ONCE per step.  A lane's WHOLE share of its row is requested up front and kept in registers:
+// the weights do not depend on the previous kernel's output, the input vector does, so the prologue's dependent loads (x, gamma, beta) wait under them - slot 0's
+// prologue issues them right behind its own small operands; they are issued before everything when slot 0 is inactive.  The slots' input vectors go through LDS G at a
+// time - all of them when the form's K <= 1024 (every LayerNorm / merge prologue), two per pass for the K <= 4096 forms (static LDS: 8 x 16.6 KB do not fit) - with a
+// barrier between the passes, which does not touch any lane's order of accumulation.  A slot whose flag (Lm1Dyn::pad0) is clear is skipped: no pointer of it is read,
+// nothing of it is written.  NBT = 0 reads no flag, takes p.dyn / p.st as the one sequence's and publishes the position as the first kernel of a step does.
 typedef unsigned lm1_u32x2 __attribute__((ext_vector_type(2)));
-// RPG: output rows per 16-lane group (4 RPG rows per workgroup).  A row's products and their order do not depend on it; what does is how much of the prologue (the input
-// vector, its LayerNorm, the barrier) a workgroup pays per byte of weights and how many weight bytes a CU has in flight (option "gemv_rows").
-template <int U, int NW, bool W16 = false, int RPG = 1>
+typedef unsigned lm1_u32x4 __attribute__((ext_vector_type(4)));
+constexpr int lm1_lds_slots(int KW, int SL) { return KW <= 1024 || SL < 2 ? SL : 2; }
+
+// block 0 publishes the position(s) the rest of the step reads
+static __device__ __forceinline__ void lm1_publish(const Lm1GemvArgs& p) {
+    if (blockIdx.x != 0 || (int)threadIdx.x >= max(p.nb, 1)) return;
+    if (p.set_pos == -2) p.dyn[threadIdx.x].pos = p.st[threadIdx.x].pos;
+    else if (p.set_pos >= 0 && p.nb == 0) p.dyn->pos = p.set_pos;
+}
+
+// a + the lane's products of one step, added in k order.  W16 = false: the four words of w are fp32 values, against xa.  W16 = true (the model's fp16 mode, cv_lm1_use_bf16):
+// a word is two bf16 (the lower k in the low half), widened here - the products and their order are those of the fp32 matrix rounded to bf16; two words go against
+// xa, the other two of a 16-byte load against xb.
+template <bool W16, typename V>
+static __device__ __forceinline__ float lm1_fma_step(float a, const V& w, const float4& xa, const float4& xb) {
+    if constexpr (W16) {
+        a += __uint_as_float(w[0] << 16) * xa.x; a += __uint_as_float(w[0] & 0xffff0000u) * xa.y;
+        a += __uint_as_float(w[1] << 16) * xa.z; a += __uint_as_float(w[1] & 0xffff0000u) * xa.w;
+        if constexpr (sizeof(V) == 16) {
+            a += __uint_as_float(w[2] << 16) * xb.x; a += __uint_as_float(w[2] & 0xffff0000u) * xb.y;
+            a += __uint_as_float(w[3] << 16) * xb.z; a += __uint_as_float(w[3] & 0xffff0000u) * xb.w;
+        }
+    } else {
+        a += __uint_as_float(w[0]) * xa.x; a += __uint_as_float(w[1]) * xa.y; a += __uint_as_float(w[2]) * xa.z; a += __uint_as_float(w[3]) * xa.w;
+    }
+    return a;
+}
+
+// The narrow form (gemm_conv.h's gemv_f32_kernel: same lane / wave / k order, same combine): 4 RPG output rows per workgroup, a 16-lane group per RPG rows, a lane four
+// k-values of every 64-float step (fp32: 16 bytes; W16: the SAME four as 8 bytes of the bf16 [N][Kp] matrix), the NW waves split K.
+// S: steps of a wave's share, all held in registers (4: K <= 1024; 8 with NW = 8: the K = 4096 product whose 1024 rows are only 256 workgroups; 16: K <= 4096 over 4 waves).
+// RPG: output rows per 16-lane group.  A row's products and their order do not depend on it; what does is how much of the prologue (the input vector, its LayerNorm,
+// the barrier) a workgroup pays per byte of weights and how many weight bytes a CU has in flight (options "gemv_rows" / "gemv_rows16": the single sequence only).
+template <int S, int NW, bool W16, int NBT, int RPG = 1>
 static __global__ __launch_bounds__(64 * NW) void lm1_gemv_kernel(Lm1GemvArgs p) {
-    __shared__ float xs[LM1_MAX_K + 64];
-    __shared__ float part[NW][4 * RPG];
-    __shared__ float mw[256];
+    static_assert(RPG == 1 || NBT == 0, "rows per group are an option of the single sequence");
+    constexpr int SL = NBT ? NBT : 1, KW = S * NW * 64, G = lm1_lds_slots(KW, SL), XS = KW + 64;       // KW: the longest input the registers cover
+    __shared__ __attribute__((aligned(16))) float xs[G * XS];
+    __shared__ float part[SL][NW][4 * RPG];
+    __shared__ float mw[G][256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4, sub = lane & 15;
     const int steps = (p.Kp + 63) / 64;
-    if (p.set_pos >= 0 && blockIdx.x == 0 && tid == 0) p.dyn->pos = p.set_pos;
-    if (p.set_pos == -2 && blockIdx.x == 0 && tid == 0) p.dyn->pos = p.st->pos;
+    lm1_publish(p);
+    bool on[SL];
+#pragma unroll
+    for (int s = 0; s < SL; ++s) on[s] = NBT == 0 || (s < p.nb && p.dyn[min(s, p.nb - 1)].pad0 != 0);
     const int row0 = ((int)blockIdx.x * 4 + grp) * RPG;           // this group's rows row0 .. row0 + RPG - 1 (clamped below: the reductions are wave collectives)
     const int s0 = wave * steps / NW, s1 = (wave + 1) * steps / NW;
-    using raw_t = typename std::conditional<W16, lm1_u32x2, v4f>::type;
-    raw_t w[RPG][U], wn[RPG][U];
-    auto load_w = [&](raw_t (&dst)[RPG][U], int sb) {
+    using raw_t = typename std::conditional<W16, lm1_u32x2, lm1_u32x4>::type;
+    raw_t w[RPG][S];
+    auto load_all = [&] {
 #pragma unroll
         for (int i = 0; i < RPG; ++i) {
             const long long ro = (long long)min(row0 + i, p.N - 1) * p.ldw;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {                       // unconditional loads (clamped step) keep the vmcnt bookkeeping exact
-                const int k = min(min(sb + u, s1 - 1) * 64 + sub * 4, p.Kp - 4);
-                if constexpr (W16) dst[i][u] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x2*>(reinterpret_cast<const unsigned short*>(p.W) + ro + k));
-                else dst[i][u] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p.W + ro + k));
+            for (int u = 0; u < S; ++u) {                       // unconditional loads (clamped step) keep the vmcnt bookkeeping exact
+                const int k = min(min(s0 + u, max(s1 - 1, 0)) * 64 + sub * 4, p.Kp - 4);
+                if constexpr (W16) w[i][u] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x2*>(reinterpret_cast<const unsigned short*>(p.W) + ro + k));
+                else w[i][u] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x4*>(p.W + ro + k));
             }
         }
     };
-    auto wide = [](const raw_t& r) -> v4f {
-        if constexpr (W16) return (v4f){__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16), __uint_as_float(r[1] & 0xffff0000u)};
-        else return r;
-    };
-    lm1_gemv_prologue<NW>(p, xs, mw, steps, [&] { if (s0 < s1) load_w(w, s0); });
-    __syncthreads();
-    // ---- the rows' dot products (gemv_f32_kernel: same loads, same order)
-    float acc[RPG];
+    if (!on[0]) load_all();                                     // (slot 0's prologue requests them behind its own small operands)
+    float acc[SL][RPG];
 #pragma unroll
-    for (int i = 0; i < RPG; ++i) acc[i] = 0.f;
-    for (int sb = s0; sb < s1; sb += U) {
-        const bool more = sb + U < s1;
-        if (more) load_w(wn, sb + U);                           // the next group is requested before this one is consumed
-        float4 x[U];
+    for (int s = 0; s < SL; ++s)
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = min(sb + u, s1 - 1) * 64 + sub * 4;
-            x[u] = *reinterpret_cast<const float4*>(&xs[k]);
-            if (sb + u >= s1) x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        for (int i = 0; i < RPG; ++i) acc[s][i] = 0.f;
 #pragma unroll
-        for (int i = 0; i < RPG; ++i)
-#pragma unroll
-            for (int u = 0; u < U; ++u) { const v4f wf = wide(w[i][u]); acc[i] += wf[0] * x[u].x; acc[i] += wf[1] * x[u].y; acc[i] += wf[2] * x[u].z; acc[i] += wf[3] * x[u].w; }
-        if (more) {
-#pragma unroll
-            for (int i = 0; i < RPG; ++i)
-#pragma unroll
-                for (int u = 0; u < U; ++u) w[i][u] = wn[i][u];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < RPG; ++i) {
-        const float a = group16_sum(acc[i]);
-        if (sub == 0) part[wave][grp * RPG + i] = a;
-    }
-    __syncthreads();
-    if (wave != 0 || sub >= RPG) return;
-    const int gi = grp * RPG + sub, n = row0 + sub;              // lane `sub` of the group finishes its row `sub`
-    if (n >= p.N) return;
-    float v = ((part[0][gi] + part[1][gi]) + part[2][gi]) + part[3][gi];
-    if (NW == 8) v = (((v + part[4 % NW][gi]) + part[5 % NW][gi]) + part[6 % NW][gi]) + part[7 % NW][gi];
-    if (p.bias) v += p.bias[n];
-    v = apply_act(p.act, v, 0.f);
-    if (p.res) v += p.res[n];
-    float* y = p.layer >= 0 ? p.dyn->rows[p.layer] + (long long)p.dyn->pos * p.N : p.y;
-    y[n] = v;
-}
-
-// The bf16 matrices again, laid out over the lanes the way the CosyVoice2 decode GEMVs are (llm_kernels.h gemv_norm_kernel), round 6: a 16-lane group owns ROWS whole rows
-// and a lane 8 consecutive k-values per 128-float step as ONE 16-byte load, every load of the workgroup's share requested before the prologue's barrier.
-//   KSPLIT = false: a wave's four groups keep their rows to themselves over the whole K (K <= 128 STEPS) - 4 NW ROWS rows per workgroup, e.g. 256 workgroups for the
-//                   [4096][1024] products: the input row and its LayerNorm are made once per 16 rows instead of once per 4 (lm1_gemv_kernel: 1024 workgroups, each
-//                   re-reading 16 KB of x / gamma / beta against 8 KB of weights);
-//   KSPLIT = true:  the NW waves share 4 ROWS rows and split K (the [1024][4096] product and the products with few rows), partial sums combined in wave order.
-// The k order of a row's sum differs from lm1_gemv_kernel's: results agree to fp32 rounding, the bf16 weights are the same values (option "gemv16_wide", default 1).
-typedef unsigned lm1_u32x4 __attribute__((ext_vector_type(4)));
-// W16 = false: the same layout over fp32 matrices (a step = 16 lanes x 4 floats = 64 k-values; KSPLIT = false only: the split forms ARE lm1_gemv_kernel's) - option "gemv_wide".
-template <bool W16, int STEPS, int ROWS, int NW, bool KSPLIT>
-static __global__ __launch_bounds__(64 * NW) void lm1_gemv16_kernel(Lm1GemvArgs p) {
-    constexpr int SK = W16 ? 128 : 64, LK = W16 ? 8 : 4;        // k-values per step / per lane and step
-    __shared__ __attribute__((aligned(16))) float xs[LM1_MAX_K + 64];
-    __shared__ float part[NW][4 * ROWS];
-    __shared__ float mw[256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4, sub = lane & 15;
-    const int steps = p.Kp / SK;                                 // steps of a row (the launcher checks Kp % SK == 0)
-    if (p.set_pos >= 0 && blockIdx.x == 0 && tid == 0) p.dyn->pos = p.set_pos;
-    if (p.set_pos == -2 && blockIdx.x == 0 && tid == 0) p.dyn->pos = p.st->pos;
-    const int unit = KSPLIT ? (int)blockIdx.x * 4 + grp : ((int)blockIdx.x * NW + wave) * 4 + grp;
-    const int row0 = unit * ROWS;
-    const int s0 = KSPLIT ? wave * steps / NW : 0, s1 = KSPLIT ? (wave + 1) * steps / NW : steps;
-    lm1_u32x4 w[ROWS][STEPS];
-    lm1_gemv_prologue<NW>(p, xs, mw, steps * SK / 64, [&] {
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            const long long ro = (long long)min(row0 + r, p.N - 1) * p.ldw + sub * LK;
-#pragma unroll
-            for (int s = 0; s < STEPS; ++s) {                     // unconditional loads (clamped step): the vmcnt bookkeeping stays exact
-                const long long k = ro + (long long)min(s0 + s, max(s1 - 1, 0)) * SK;
-                if constexpr (W16) w[r][s] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x4*>(reinterpret_cast<const unsigned short*>(p.W) + k));
-                else w[r][s] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x4*>(p.W + k));
-            }
-        }
-    });
-    __syncthreads();
-    float acc[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < STEPS; ++s) {
-        if (s0 + s < s1) {
-            const float4 xa = *reinterpret_cast<const float4*>(&xs[(s0 + s) * SK + sub * LK]);
-            float4 xb = xa;
-            if constexpr (W16) xb = *reinterpret_cast<const float4*>(&xs[(s0 + s) * SK + sub * LK + 4]);
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const lm1_u32x4 u = w[r][s];
-                float a = acc[r];
-                if constexpr (W16) {
-                    a += __uint_as_float(u[0] << 16) * xa.x;          a += __uint_as_float(u[0] & 0xffff0000u) * xa.y;
-                    a += __uint_as_float(u[1] << 16) * xa.z;          a += __uint_as_float(u[1] & 0xffff0000u) * xa.w;
-                    a += __uint_as_float(u[2] << 16) * xb.x;          a += __uint_as_float(u[2] & 0xffff0000u) * xb.y;
-                    a += __uint_as_float(u[3] << 16) * xb.z;          a += __uint_as_float(u[3] & 0xffff0000u) * xb.w;
-                } else {
-                    a += __uint_as_float(u[0]) * xa.x; a += __uint_as_float(u[1]) * xa.y; a += __uint_as_float(u[2]) * xa.z; a += __uint_as_float(u[3]) * xa.w;
-                }
-                acc[r] = a;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = group16_sum(acc[r]);
-    if constexpr (KSPLIT) {
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) if (sub == 0) part[wave][grp * ROWS + r] = acc[r];
-        __syncthreads();
-        if (wave != 0) return;
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) { float t = 0.f; for (int ww = 0; ww < NW; ++ww) t += part[ww][grp * ROWS + r]; acc[r] = t; }
-    }
-    if (sub != 0) return;
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-        const int n = row0 + r;
-        if (n < p.N) {
-            float v = acc[r];
-            if (p.bias) v += p.bias[n];
-            v = apply_act(p.act, v, 0.f);
-            if (p.res) v += p.res[n];
-            float* y = p.layer >= 0 ? p.dyn->rows[p.layer] + (long long)p.dyn->pos * p.N : p.y;
-            y[n] = v;
-        }
-    }
-}
-
-// ---- lock-step batched decode (cv_lm1_batch_*): the same products for up to LM1_MAX_SLOTS sequences, every weight row read ONCE per step ---------------------------
-// A lane owns the (row, k-subset) it owns in the single-sequence kernel and carries one accumulator per slot: for every slot the products, their order, the 16-lane
-// reduction and the combine of the waves' partial sums are those of the kernel gemv() picks for the same (N, K, dtype, prologue), so a slot's output has the bits of
-// cv_lm1_step on that sequence alone - whatever the slot count and whichever slot it sits in.  What differs is the schedule: a lane's WHOLE share of its row is
-// requested up front and kept in registers (at most 16 steps: K <= 4096 over 4 waves), and the slots' input vectors go through LDS G at a time - all of them when
-// K <= 1024 (every LayerNorm / merge prologue), two per pass for the K <= 4096 products (static LDS: 8 x 16.6 KB do not fit) - with a barrier between the passes,
-// which does not touch any lane's order of accumulation.  A slot whose flag (Lm1Dyn::pad0) is clear is skipped: no pointer of it is read, nothing of it is written.
-constexpr int LM1_MAX_SLOTS = 8;
-struct Lm1BGemvArgs {
-    Lm1GemvArgs a;                             // slot 0's x / res / y; the matrix, bias, gamma / beta are shared; a.dyn / a.st are unused (dyns / sts below)
-    long long sx, sres, sy;                    // floats between two slots' x / res / y
-    Lm1Dyn* dyns;                              // [nb]: position, cache rows, tables, flag (pad0 != 0: the slot takes part in the step)
-    const DecodeState* sts;                    // [nb] (a.set_pos == -2: block 0 publishes every slot's position)
-    int nb;
-};
-
-static __device__ __forceinline__ void lm1b_publish(const Lm1BGemvArgs& q) {
-    if (q.a.set_pos == -2 && blockIdx.x == 0 && (int)threadIdx.x < q.nb) q.dyns[threadIdx.x].pos = q.sts[threadIdx.x].pos;
-}
-
-// lm1_gemv_kernel<U, NW, W16> for NBT slots; S: steps of a lane's share held in registers (4: U = 4 forms, steps <= 16; 8: NW = 8; 16: U = 8, NW = 4), KW: longest input.
-template <int S, int NW, bool W16, int NBT, int G, int KW>
-static __global__ __launch_bounds__(64 * NW) void lm1_gemvb_kernel(Lm1BGemvArgs q) {
-    constexpr int XS = KW + 64;
-    __shared__ __attribute__((aligned(16))) float xs[G * XS];
-    __shared__ float part[NBT][NW][4];
-    __shared__ float mw[G][256];
-    const Lm1GemvArgs& p = q.a;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4, sub = lane & 15;
-    const int steps = (p.Kp + 63) / 64;
-    lm1b_publish(q);
-    bool on[NBT];
-#pragma unroll
-    for (int s = 0; s < NBT; ++s) on[s] = s < q.nb && q.dyns[min(s, q.nb - 1)].pad0 != 0;
-    const int row0 = (int)blockIdx.x * 4 + grp;
-    const int s0 = wave * steps / NW, s1 = (wave + 1) * steps / NW;
-    using raw_t = typename std::conditional<W16, lm1_u32x2, v4f>::type;
-    raw_t w[S];
-    auto load_all = [&] {
-        const long long ro = (long long)min(row0, p.N - 1) * p.ldw;
-#pragma unroll
-        for (int u = 0; u < S; ++u) {                           // unconditional loads (clamped step)
-            const int k = min(min(s0 + u, max(s1 - 1, 0)) * 64 + sub * 4, p.Kp - 4);
-            if constexpr (W16) w[u] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x2*>(reinterpret_cast<const unsigned short*>(p.W) + ro + k));
-            else w[u] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p.W + ro + k));
-        }
-    };
-    auto wide = [](const raw_t& r) -> v4f {
-        if constexpr (W16) return (v4f){__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16), __uint_as_float(r[1] & 0xffff0000u)};
-        else return r;
-    };
-    if (!on[0]) load_all();                                     // (slot 0's prologue requests them behind its own small operands, like the single-sequence kernel)
-    float acc[NBT];
-#pragma unroll
-    for (int s = 0; s < NBT; ++s) acc[s] = 0.f;
-#pragma unroll
-    for (int p0 = 0; p0 < NBT; p0 += G) {
+    for (int p0 = 0; p0 < SL; p0 += G) {
         if (p0 > 0) __syncthreads();                            // every lane is done with the previous pass's vectors
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const int sl = p0 + g;
             if (on[sl]) {
                 Lm1GemvArgs ps = p;
-                ps.x = p.x + sl * q.sx;
+                ps.x = p.x + sl * p.sx;
                 lm1_gemv_prologue<NW>(ps, xs + g * XS, mw[g], steps, [&] { if (sl == 0) load_all(); });
             }
         }
         __syncthreads();
+        // ---- the rows' dot products (gemv_f32_kernel: same loads, same order)
 #pragma unroll
         for (int u = 0; u < S; ++u) {
             if (s0 + u < s1) {
-                const v4f wf = wide(w[u]);
                 const int k = (s0 + u) * 64 + sub * 4;
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
                     if (on[p0 + g]) {
                         const float4 x = *reinterpret_cast<const float4*>(&xs[g * XS + k]);
-                        float a = acc[p0 + g];
-                        a += wf[0] * x.x; a += wf[1] * x.y; a += wf[2] * x.z; a += wf[3] * x.w;
-                        acc[p0 + g] = a;
+#pragma unroll
+                        for (int i = 0; i < RPG; ++i) acc[p0 + g][i] = lm1_fma_step<W16>(acc[p0 + g][i], w[i][u], x, x);
                     }
                 }
             }
         }
     }
 #pragma unroll
-    for (int s = 0; s < NBT; ++s) {
+    for (int s = 0; s < SL; ++s) {
         if (on[s]) {
-            const float a = group16_sum(acc[s]);
-            if (sub == 0) part[s][wave][grp] = a;
+#pragma unroll
+            for (int i = 0; i < RPG; ++i) {
+                const float a = group16_sum(acc[s][i]);
+                if (sub == 0) part[s][wave][grp * RPG + i] = a;
+            }
         }
     }
     __syncthreads();
-    if (wave != 0 || sub >= q.nb || sub >= NBT) return;         // lane `sub` of the group finishes slot `sub`
-    const int sl = sub, n = row0;
-    if (n >= p.N || q.dyns[sl].pad0 == 0) return;
-    float v = ((part[sl][0][grp] + part[sl][1][grp]) + part[sl][2][grp]) + part[sl][3][grp];
-    if (NW == 8) v = (((v + part[sl][4 % NW][grp]) + part[sl][5 % NW][grp]) + part[sl][6 % NW][grp]) + part[sl][7 % NW][grp];
+    static_assert(RPG * SL <= 16, "a lane of the group per (row, slot)");
+    const int sl = sub / RPG, gi = grp * RPG + sub % RPG, n = row0 + sub % RPG;      // lane `sub` of wave 0's group finishes row `sub % RPG` of slot `sub / RPG`
+    if (wave != 0 || sl >= (NBT ? min(p.nb, NBT) : 1) || n >= p.N) return;
+    if (NBT != 0 && p.dyn[sl].pad0 == 0) return;
+    float v = ((part[sl][0][gi] + part[sl][1][gi]) + part[sl][2][gi]) + part[sl][3][gi];
+    if (NW == 8) v = (((v + part[sl][4 % NW][gi]) + part[sl][5 % NW][gi]) + part[sl][6 % NW][gi]) + part[sl][7 % NW][gi];
     if (p.bias) v += p.bias[n];
     v = apply_act(p.act, v, 0.f);
-    if (p.res) v += p.res[sl * q.sres + n];
-    float* y = p.layer >= 0 ? q.dyns[sl].rows[p.layer] + (long long)q.dyns[sl].pos * p.N : p.y + sl * q.sy;
+    if (p.res) v += p.res[sl * p.sres + n];
+    float* y = p.layer >= 0 ? p.dyn[sl].rows[p.layer] + (long long)p.dyn[sl].pos * p.N : p.y + sl * p.sy;
     y[n] = v;
 }
 
-// lm1_gemv16_kernel<W16, STEPS, 1, NW, KSPLIT> for NBT slots (its weights already sit in registers for the whole row share).
-template <bool W16, int STEPS, int NW, bool KSPLIT, int NBT, int G, int KW>
-static __global__ __launch_bounds__(64 * NW) void lm1_gemv16b_kernel(Lm1BGemvArgs q) {
-    constexpr int SK = W16 ? 128 : 64, LK = W16 ? 8 : 4;
-    constexpr int XS = KW + 64;
+// The wide form, laid out over the lanes the way the CosyVoice2 decode GEMVs are (llm_kernels.h gemv_norm_kernel), round 6: a 16-lane group owns a whole row and a lane
+// ONE 16-byte load per step - W16: 8 consecutive k-values of a 128-float step of the bf16 matrix (option "gemv16_wide", default 1); W16 = false: 4 of a 64-float step of
+// the fp32 matrix (option "gemv_wide"; KSPLIT = false only: the split forms ARE lm1_gemv_kernel's).  STEPS: steps of a lane's share, all held in registers.
+//   KSPLIT = false: a wave's four groups keep their rows to themselves over the whole K (K <= STEPS steps) - 4 NW rows per workgroup, e.g. 256 workgroups for the
+//                   [4096][1024] products: the input row and its LayerNorm are made once per 16 rows instead of once per 4 (lm1_gemv_kernel: 1024 workgroups, each
+//                   re-reading 16 KB of x / gamma / beta against 8 KB of weights);
+//   KSPLIT = true:  the NW waves share 4 rows and split K (the [1024][4096] product and the products with few rows), partial sums combined in wave order.
+// The k order of a row's sum differs from lm1_gemv_kernel's: results agree to fp32 rounding, the weights are the same values.
+template <bool W16, int STEPS, int NW, bool KSPLIT, int NBT>
+static __global__ __launch_bounds__(64 * NW) void lm1_gemv16_kernel(Lm1GemvArgs p) {
+    constexpr int SK = W16 ? 128 : 64, LK = W16 ? 8 : 4;        // k-values per step / per lane and step
+    // KW: the input LDS of a slot - the longest K the registers cover; the single sequence keeps the LM1_MAX_K it had before the kernel took slots (1024 measures the same:
+    // profiles/lm1_gemv_fold_ab.txt)
+    constexpr int SL = NBT ? NBT : 1, KW = NBT ? STEPS * SK * (KSPLIT ? NW : 1) : LM1_MAX_K, G = lm1_lds_slots(KW, SL), XS = KW + 64;
     __shared__ __attribute__((aligned(16))) float xs[G * XS];
-    __shared__ float part[NBT][NW][4];
+    __shared__ float part[SL][NW][4];
     __shared__ float mw[G][256];
-    const Lm1GemvArgs& p = q.a;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4, sub = lane & 15;
-    const int steps = p.Kp / SK;
-    lm1b_publish(q);
-    bool on[NBT];
+    const int steps = p.Kp / SK;                                 // steps of a row (pick_form checks Kp % SK == 0)
+    lm1_publish(p);
+    bool on[SL];
 #pragma unroll
-    for (int s = 0; s < NBT; ++s) on[s] = s < q.nb && q.dyns[min(s, q.nb - 1)].pad0 != 0;
+    for (int s = 0; s < SL; ++s) on[s] = NBT == 0 || (s < p.nb && p.dyn[min(s, p.nb - 1)].pad0 != 0);
     const int row0 = KSPLIT ? (int)blockIdx.x * 4 + grp : ((int)blockIdx.x * NW + wave) * 4 + grp;
     const int s0 = KSPLIT ? wave * steps / NW : 0, s1 = KSPLIT ? (wave + 1) * steps / NW : steps;
     lm1_u32x4 w[STEPS];
     auto load_all = [&] {
         const long long ro = (long long)min(row0, p.N - 1) * p.ldw + sub * LK;
 #pragma unroll
-        for (int s = 0; s < STEPS; ++s) {
+        for (int s = 0; s < STEPS; ++s) {                       // unconditional loads (clamped step): the vmcnt bookkeeping stays exact
             const long long k = ro + (long long)min(s0 + s, max(s1 - 1, 0)) * SK;
             if constexpr (W16) w[s] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x4*>(reinterpret_cast<const unsigned short*>(p.W) + k));
             else w[s] = __builtin_nontemporal_load(reinterpret_cast<const lm1_u32x4*>(p.W + k));
-        }
+            order_memory();                                     // requested in the order the steps are consumed: vmcnt retires in issue order, and left alone the scheduler
+        }                                                       // issues step 0 seventh of eight - the first product then waits for seven loads (10 % of the whole-row forms' time)
     };
     if (!on[0]) load_all();
-    float acc[NBT];
+    float acc[SL];
 #pragma unroll
-    for (int s = 0; s < NBT; ++s) acc[s] = 0.f;
+    for (int s = 0; s < SL; ++s) acc[s] = 0.f;
 #pragma unroll
-    for (int p0 = 0; p0 < NBT; p0 += G) {
+    for (int p0 = 0; p0 < SL; p0 += G) {
         if (p0 > 0) __syncthreads();
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const int sl = p0 + g;
             if (on[sl]) {
                 Lm1GemvArgs ps = p;
-                ps.x = p.x + sl * q.sx;
+                ps.x = p.x + sl * p.sx;
                 lm1_gemv_prologue<NW>(ps, xs + g * XS, mw[g], steps * SK / 64, [&] { if (sl == 0) load_all(); });
             }
         }
@@ -479,48 +348,39 @@ static __global__ __launch_bounds__(64 * NW) void lm1_gemv16b_kernel(Lm1BGemvArg
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) {
             if (s0 + s < s1) {
-                const lm1_u32x4 u = w[s];
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
                     if (on[p0 + g]) {
                         const float* xg = &xs[g * XS + (s0 + s) * SK + sub * LK];
                         const float4 xa = *reinterpret_cast<const float4*>(xg);
-                        float a = acc[p0 + g];
-                        if constexpr (W16) {
-                            const float4 xb = *reinterpret_cast<const float4*>(xg + 4);
-                            a += __uint_as_float(u[0] << 16) * xa.x;          a += __uint_as_float(u[0] & 0xffff0000u) * xa.y;
-                            a += __uint_as_float(u[1] << 16) * xa.z;          a += __uint_as_float(u[1] & 0xffff0000u) * xa.w;
-                            a += __uint_as_float(u[2] << 16) * xb.x;          a += __uint_as_float(u[2] & 0xffff0000u) * xb.y;
-                            a += __uint_as_float(u[3] << 16) * xb.z;          a += __uint_as_float(u[3] & 0xffff0000u) * xb.w;
-                        } else {
-                            a += __uint_as_float(u[0]) * xa.x; a += __uint_as_float(u[1]) * xa.y; a += __uint_as_float(u[2]) * xa.z; a += __uint_as_float(u[3]) * xa.w;
-                        }
-                        acc[p0 + g] = a;
+                        float4 xb = xa;
+                        if constexpr (W16) xb = *reinterpret_cast<const float4*>(xg + 4);
+                        acc[p0 + g] = lm1_fma_step<W16>(acc[p0 + g], w[s], xa, xb);
                     }
                 }
             }
         }
     }
 #pragma unroll
-    for (int s = 0; s < NBT; ++s) if (on[s]) acc[s] = group16_sum(acc[s]);
+    for (int s = 0; s < SL; ++s) if (on[s]) acc[s] = group16_sum(acc[s]);
     if constexpr (KSPLIT) {
 #pragma unroll
-        for (int s = 0; s < NBT; ++s) if (on[s] && sub == 0) part[s][wave][grp] = acc[s];
+        for (int s = 0; s < SL; ++s) if (on[s] && sub == 0) part[s][wave][grp] = acc[s];
         __syncthreads();
         if (wave != 0) return;
 #pragma unroll
-        for (int s = 0; s < NBT; ++s) if (on[s]) { float t = 0.f; for (int ww = 0; ww < NW; ++ww) t += part[s][ww][grp]; acc[s] = t; }
+        for (int s = 0; s < SL; ++s) if (on[s]) { float t = 0.f; for (int ww = 0; ww < NW; ++ww) t += part[s][ww][grp]; acc[s] = t; }
     }
     if (sub != 0 || row0 >= p.N) return;
     const int n = row0;
 #pragma unroll
-    for (int s = 0; s < NBT; ++s) {
+    for (int s = 0; s < SL; ++s) {
         if (on[s]) {
             float v = acc[s];
             if (p.bias) v += p.bias[n];
             v = apply_act(p.act, v, 0.f);
-            if (p.res) v += p.res[s * q.sres + n];
-            float* y = p.layer >= 0 ? q.dyns[s].rows[p.layer] + (long long)q.dyns[s].pos * p.N : p.y + s * q.sy;
+            if (p.res) v += p.res[s * p.sres + n];
+            float* y = p.layer >= 0 ? p.dyn[s].rows[p.layer] + (long long)p.dyn[s].pos * p.N : p.y + s * p.sy;
             y[n] = v;
         }
     }
@@ -701,18 +561,17 @@ hipStream_t resolve(cv_lm1* m, void* s) {
 }
 
 // ---- the kernel form of a decode GEMV ---------------------------------------------------------------------------------------------------------------------
-// ONE table for the single-sequence step and the lock-step batch: a slot of the batch goes through the batched twin of the kernel the single step picks for the same
-// (N, K, dtype, prologue), and that is what keeps a slot's bits those of the single step.
-//   form             single sequence                             slots of the batch (NBT slots, G vectors in LDS at a time, longest input)
-enum Lm1Form {
-    LM1_F16_ROWS,   // lm1_gemv16_kernel<true, 8, 1, 4, false>     lm1_gemv16b_kernel<true, 8, 4, false, NBT, all, 1024>      bf16, 16-byte loads, 16 whole rows per workgroup
-    LM1_F16_SPLIT,  // lm1_gemv16_kernel<true, 2, 1, 4, true>      lm1_gemv16b_kernel<true, 2, 4, true, NBT, all, 1024>       bf16, 4 waves split K
-    LM1_F16_SPLIT8, // lm1_gemv16_kernel<true, 4, 1, 8, true>      lm1_gemv16b_kernel<true, 4, 8, true, NBT, two, 4096>       bf16, 8 waves split K
-    LM1_F32_ROWS,   // lm1_gemv16_kernel<false, 16, 1, 4, false>   lm1_gemv16b_kernel<false, 16, 4, false, NBT, all, 1024>    fp32, 16 whole rows per workgroup
-    LM1_U4,         // lm1_gemv_kernel<4, 4, W16, RPG>             lm1_gemvb_kernel<4, 4, W16, NBT, all, 1024>                a wave's share is at most 4 steps
-    LM1_U8_NW8,     // lm1_gemv_kernel<8, 8, W16, RPG>             lm1_gemvb_kernel<8, 8, W16, NBT, two, 4096>                8 waves, 8 steps each
-    LM1_U8          // lm1_gemv_kernel<8, 4, W16, RPG>             lm1_gemvb_kernel<16, 4, W16, NBT, two, 4096>               U = 8 in flight, NW = 4: the 16 steps of a wave's share
-};                  //                                                                                                       are what the batched kernel holds in registers (S = 16)
+// ONE table for the single-sequence step (NBT = 0) and the lock-step batch (NBT = 1 / 2 / 4 / 8 slots): a slot of the batch goes through another instantiation of the
+// kernel the single step picks for the same (N, K, dtype, prologue), and that is what keeps a slot's bits those of the single step.
+enum Lm1Form {      // kernel                                               longest K (the slots' vectors in LDS at a time; NBT = 0 of lm1_gemv16_kernel: LDS for 4096)
+    LM1_F16_ROWS,   // lm1_gemv16_kernel<true, 8, 4, false, NBT>            1024 (all)   bf16, 16-byte loads, 16 whole rows per workgroup
+    LM1_F16_SPLIT,  // lm1_gemv16_kernel<true, 2, 4, true, NBT>             1024 (all)   bf16, 4 waves split K
+    LM1_F16_SPLIT8, // lm1_gemv16_kernel<true, 4, 8, true, NBT>             4096 (two)   bf16, 8 waves split K
+    LM1_F32_ROWS,   // lm1_gemv16_kernel<false, 16, 4, false, NBT>          1024 (all)   fp32, 16 whole rows per workgroup
+    LM1_U4,         // lm1_gemv_kernel<4, 4, W16, NBT, RPG>                 1024 (all)   a wave's share is at most 4 steps
+    LM1_U8_NW8,     // lm1_gemv_kernel<8, 8, W16, NBT, RPG>                 4096 (two)   8 waves, 8 steps each
+    LM1_U8          // lm1_gemv_kernel<16, 4, W16, NBT, RPG>                4096 (two)   4 waves, 16 steps each
+};
 struct Lm1Pick { Lm1Form form; int rows; bool rpg; };      // rows: output rows per workgroup; rpg: an lm1_gemv_kernel form (single sequence: rows times RPG, option "gemv_rows")
 
 Lm1Pick pick_form(bool h16, int wide16, int wide32, int pro, int N, int K) {
@@ -747,24 +606,28 @@ Lm1Loop loop_batch(cv_lm1* m) {
     return {B.sps.as<SampleParams>(), B.tokens.as<int>(), B.xin.as<float>(), B.logits.as<float>(), B.uniforms.as<float>(), B.emb_table, B.tok_cap, B.uni_cap};
 }
 
+// the launch of form f for NBT slots (0: the single sequence, the only one with rpg > 1 rows per lane group)
 template <int NBT>
-void gemvb_n(Lm1Pick f, bool h16, const Lm1BGemvArgs& q, hipStream_t s) {
-    constexpr int GA = NBT, GB = NBT < 2 ? NBT : 2;            // slots' vectors in LDS at a time: all (K <= 1024) / two (K <= 4096)
-    const dim3 grid((unsigned)((q.a.N + f.rows - 1) / f.rows));
-#define LM1_GEMV16B(W16_, STEPS_, NW_, KSPLIT_, G_, KW_) hipLaunchKernelGGL((lm1_gemv16b_kernel<W16_, STEPS_, NW_, KSPLIT_, NBT, G_, KW_>), grid, dim3(64 * NW_), 0, s, q)
-#define LM1_GEMVB(S_, NW_, G_, KW_) do { if (h16) hipLaunchKernelGGL((lm1_gemvb_kernel<S_, NW_, true, NBT, G_, KW_>), grid, dim3(64 * NW_), 0, s, q); \
-                                         else hipLaunchKernelGGL((lm1_gemvb_kernel<S_, NW_, false, NBT, G_, KW_>), grid, dim3(64 * NW_), 0, s, q); } while (0)
+void launch_gemv(Lm1Pick f, bool h16, int rpg, const Lm1GemvArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)((a.N + f.rows * rpg - 1) / (f.rows * rpg)));
+#define LM1_GEMV16(W16_, STEPS_, NW_, KSPLIT_) hipLaunchKernelGGL((lm1_gemv16_kernel<W16_, STEPS_, NW_, KSPLIT_, NBT>), grid, dim3(64 * NW_), 0, s, a)
+#define LM1_GEMV(S_, NW_, W16_, RPG_) hipLaunchKernelGGL((lm1_gemv_kernel<S_, NW_, W16_, NBT, RPG_>), grid, dim3(64 * NW_), 0, s, a)
+#define LM1_GEMV_R(S_, NW_, W16_) do { if constexpr (NBT != 0) LM1_GEMV(S_, NW_, W16_, 1); else if (rpg == 4) LM1_GEMV(S_, NW_, W16_, 4); \
+                                       else if (rpg == 2) LM1_GEMV(S_, NW_, W16_, 2); else LM1_GEMV(S_, NW_, W16_, 1); } while (0)
+#define LM1_GEMV_H(S_, NW_) do { if (h16) LM1_GEMV_R(S_, NW_, true); else LM1_GEMV_R(S_, NW_, false); } while (0)
     switch (f.form) {
-    case LM1_F16_ROWS:   LM1_GEMV16B(true, 8, 4, false, GA, 1024); break;
-    case LM1_F16_SPLIT:  LM1_GEMV16B(true, 2, 4, true, GA, 1024); break;
-    case LM1_F16_SPLIT8: LM1_GEMV16B(true, 4, 8, true, GB, LM1_MAX_K); break;
-    case LM1_F32_ROWS:   LM1_GEMV16B(false, 16, 4, false, GA, 1024); break;
-    case LM1_U4:         LM1_GEMVB(4, 4, GA, 1024); break;
-    case LM1_U8_NW8:     LM1_GEMVB(8, 8, GB, LM1_MAX_K); break;
-    case LM1_U8:         LM1_GEMVB(16, 4, GB, LM1_MAX_K); break;
+    case LM1_F16_ROWS:   LM1_GEMV16(true, 8, 4, false); break;
+    case LM1_F16_SPLIT:  LM1_GEMV16(true, 2, 4, true); break;
+    case LM1_F16_SPLIT8: LM1_GEMV16(true, 4, 8, true); break;
+    case LM1_F32_ROWS:   LM1_GEMV16(false, 16, 4, false); break;
+    case LM1_U4:         LM1_GEMV_H(4, 4); break;
+    case LM1_U8_NW8:     LM1_GEMV_H(8, 8); break;
+    case LM1_U8:         LM1_GEMV_H(16, 4); break;
     }
-#undef LM1_GEMVB
-#undef LM1_GEMV16B
+#undef LM1_GEMV_H
+#undef LM1_GEMV_R
+#undef LM1_GEMV
+#undef LM1_GEMV16
 }
 
 // One decode GEMV on q's sequence or slots (sx / sres / sy: floats between two slots' x / res / y).  W16: the bf16 copy of W (cv_lm1_use_bf16) or null
@@ -773,34 +636,12 @@ void gemv(cv_lm1* m, const Lm1Seq& q, int pro, const float* x, long long sx, con
     CV_CHECK(K % 4 == 0 && K <= LM1_MAX_K && (pro != LM1_PRO_LN || K <= 1024), "cv_lm1: a GEMV input of up to 4096 floats (1024 under the LayerNorm prologue), K % 4 == 0");
     const bool h16 = m->w16 && W16 != nullptr;
     const Lm1Pick f = pick_form(h16, m->wide16, m->wide32, pro, N, K);
-    Lm1GemvArgs a{x, g, b, eps, h16 ? reinterpret_cast<const float*>(W16) : W, (long long)kp_of(K), bias, res, y, q.nb ? nullptr : q.dyn, layer, set_pos, q.nb ? nullptr : q.st, N, K, kp_of(K), act, pro};
-    if (q.nb) {
-        const Lm1BGemvArgs qa{a, sx, sres, sy, q.dyn, q.st, q.nb};
-        if (q.nb == 1) gemvb_n<1>(f, h16, qa, s);
-        else if (q.nb == 2) gemvb_n<2>(f, h16, qa, s);
-        else if (q.nb <= 4) gemvb_n<4>(f, h16, qa, s);
-        else gemvb_n<8>(f, h16, qa, s);
-        return;
-    }
-    const int rpg = !f.rpg ? 1 : h16 ? m->rows16 : m->rows32;
-    const dim3 grid((unsigned)((N + f.rows * rpg - 1) / (f.rows * rpg)));
-#define LM1_GEMV16(W16_, STEPS_, NW_, KSPLIT_) hipLaunchKernelGGL((lm1_gemv16_kernel<W16_, STEPS_, 1, NW_, KSPLIT_>), grid, dim3(64 * NW_), 0, s, a)
-#define LM1_GEMV(U_, NW_, W16_, RPG_) hipLaunchKernelGGL((lm1_gemv_kernel<U_, NW_, W16_, RPG_>), grid, dim3(64 * NW_), 0, s, a)
-#define LM1_GEMV_R(U_, NW_, W16_) do { if (rpg == 4) LM1_GEMV(U_, NW_, W16_, 4); else if (rpg == 2) LM1_GEMV(U_, NW_, W16_, 2); else LM1_GEMV(U_, NW_, W16_, 1); } while (0)
-#define LM1_GEMV_H(U_, NW_) do { if (h16) LM1_GEMV_R(U_, NW_, true); else LM1_GEMV_R(U_, NW_, false); } while (0)
-    switch (f.form) {
-    case LM1_F16_ROWS:   LM1_GEMV16(true, 8, 4, false); break;
-    case LM1_F16_SPLIT:  LM1_GEMV16(true, 2, 4, true); break;
-    case LM1_F16_SPLIT8: LM1_GEMV16(true, 4, 8, true); break;
-    case LM1_F32_ROWS:   LM1_GEMV16(false, 16, 4, false); break;
-    case LM1_U4:         LM1_GEMV_H(4, 4); break;
-    case LM1_U8_NW8:     LM1_GEMV_H(8, 8); break;
-    case LM1_U8:         LM1_GEMV_H(8, 4); break;
-    }
-#undef LM1_GEMV_H
-#undef LM1_GEMV_R
-#undef LM1_GEMV
-#undef LM1_GEMV16
+    const Lm1GemvArgs a{x, g, b, eps, h16 ? reinterpret_cast<const float*>(W16) : W, (long long)kp_of(K), bias, res, y, q.dyn, layer, set_pos, q.st, N, K, kp_of(K), act, pro, sx, sres, sy, q.nb};
+    if (q.nb == 0) launch_gemv<0>(f, h16, !f.rpg ? 1 : h16 ? m->rows16 : m->rows32, a, s);
+    else if (q.nb == 1) launch_gemv<1>(f, h16, 1, a, s);
+    else if (q.nb == 2) launch_gemv<2>(f, h16, 1, a, s);
+    else if (q.nb <= 4) launch_gemv<4>(f, h16, 1, a, s);
+    else launch_gemv<8>(f, h16, 1, a, s);
 }
 
 // The decode attention of one layer: nb == 0 is the single-sequence launch on dyn[0], nb >= 1 the batched one (blockIdx.z = slot, a slot's partials heads * LM1_SPLITS * 66

@@ -1,4 +1,4 @@
-"""The kernels of the CosyVoice-300M decode step (csrc/lm1.hip: lm1_attn_kernel, the lm1_gemv / lm1_gemv16 forms and their batched twins) against float64
+"""The kernels of the CosyVoice-300M decode step (csrc/lm1.hip: lm1_attn_kernel, the forms of lm1_gemv_kernel / lm1_gemv16_kernel for the single sequence and for the slots of the batch) against float64
 references, through the test entry points cv_lm1_attention, cv_lm1_gemv and cv_lm1_gemv_batch - the launch helpers of the step itself (launch_attn, gemv() for the single sequence and for the slots).
 
 Every operand is allocated at its exact size through lib.hook (under the emulator it ends flush against an inaccessible page); outputs carry a sentinel and spare tail
@@ -449,7 +449,8 @@ def _kp(K):
 
 
 def _form(N, K, bf16, pro, wide=1, wide16=1):
-    """gemv()'s dispatch rule (csrc/lm1.hip), restated: kp = K rounded up to 32, steps = 64-float steps of a row."""
+    """gemv()'s dispatch rule (csrc/lm1.hip pick_form), restated: kp = K rounded up to 32, steps = 64-float steps of a row.  The strings are labels of the forms only:
+    gemv<4,4> / <8,8> / <8,4> are LM1_U4 / LM1_U8_NW8 / LM1_U8 of lm1_gemv_kernel, gemv16<..> the four forms of lm1_gemv16_kernel."""
     kp = _kp(K)
     steps = (kp + 63) // 64
     if bf16 and wide16 and kp % 128 == 0:
@@ -623,7 +624,7 @@ _F32 = [("gemv<4,4,f32>", N, K) for K in (4, 36, 64, 100, 1020, 1024) for N in (
 _F32 += [("gemv16<f32,16,1,4,whole>", N, K) for K in (64, 512, 1024) for N in (2048, 2050)]
 _F32 += [("gemv<4,4,f32>", 2048, 96)]                           # kp = 96 is no multiple of 64: the whole-row form falls back to the narrow one
 _F32 += [("gemv<8,8,f32>", N, K) for K in (1028, 1280, 4092, 4096) for N in (5, 1024)]
-_F32 += [("gemv<8,4,f32>", 2052, 1088), ("gemv<8,4,f32>", 2052, 2112)]          # the form no model reaches; K = 2112: 33 steps, the last wave's share takes two rounds of U = 8
+_F32 += [("gemv<8,4,f32>", 2052, 1088), ("gemv<8,4,f32>", 2052, 2112)]          # the form no model reaches; K = 2112: 33 steps, the last wave's share is 9 of the 16 steps a lane holds
 _BF16 = [("gemv16<bf16,8,1,4,whole>", N, K) for K in (128, 1024) for N in (2048, 2050)]
 _BF16 += [("gemv16<bf16,2,1,4,ksplit>", N, K) for K in (128, 640, 1024) for N in (3, 130)]      # K = 128: three waves with no step; 640: shares 1, 1, 1, 2
 _BF16 += [("gemv16<bf16,4,1,8,ksplit>", 5, 1152), ("gemv16<bf16,4,1,8,ksplit>", 5, 4096), ("gemv16<bf16,4,1,8,ksplit>", 130, 1152)]        # st = 9: shares 1 x 7, 2
@@ -662,6 +663,23 @@ def test_gemv_rows_per_group_give_the_same_bits(lib, N):
                 ys.append(q.launch(lib, ops))
         q.check(ys[0], form, "rows N=%d K=%d" % (N, K))
         assert torch.equal(ys[0], ys[1]) and torch.equal(ys[0], ys[2])
+
+
+def test_gemv_rows_per_group_under_a_prologue(lib):
+    """gemv_rows / gemv_rows16 = 1, 2, 4 behind the LayerNorm and the merge prologue (the lane that finishes a row changes with the rows per group, the vector in
+    LDS does not): the same bits across the three, rows = 1 inside the float64 bound, nothing written behind y (launch)."""
+    for bf16, opt, N, K, pro in ((False, "gemv_rows", 5, 100, LN), (False, "gemv_rows", 130, 64, MERGE), (True, "gemv_rows16", 5, 96, LN), (True, "gemv_rows16", 130, 64, MERGE)):
+        q = Gemv(N, K, 1000 + N + K, bf16=bf16, pro=pro)
+        narrow = {"gemv16_wide": 0} if bf16 else {}
+        form = _form(N, K, bf16, pro, wide16=0 if bf16 else 1)
+        assert form.startswith("gemv<")
+        ops = q.device(lib)
+        ys = []
+        for rows in (1, 2, 4):
+            with _options(lib, **{opt: rows}, **narrow):
+                ys.append(q.launch(lib, ops))
+        q.check(ys[0], form, "rows pro=%d N=%d K=%d" % (pro, N, K))
+        assert torch.equal(ys[0], ys[1]) and torch.equal(ys[0], ys[2]), "pro=%d N=%d K=%d bf16=%s: the rows per group changed the bits" % (pro, N, K, bf16)
 
 
 def test_gemv_wide_options_off(lib):
