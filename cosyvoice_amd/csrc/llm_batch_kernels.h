@@ -686,82 +686,24 @@ static __global__ __launch_bounds__(NW * 64) void attn_decode_batch_kernel(AttnD
         }
     };
     load_pass(0, k4, v4);
-    const float* qraw = qkv + h * 64;
-    const float* kq = qkv + p.heads * 64 + g * 64;
-    const float* vq = qkv + (p.heads + p.kv_heads) * 64 + g * 64;
-    const int d0 = sub * 4, dp = (d0 + 32) & 63;
-    const float4 c4 = *reinterpret_cast<const float4*>(p.rope_cos + pos * 32 + (d0 & 31));
-    const float4 s4 = *reinterpret_cast<const float4*>(p.rope_sin + pos * 32 + (d0 & 31));
-    const float4 qa = *reinterpret_cast<const float4*>(qraw + d0), qb = *reinterpret_cast<const float4*>(qraw + dp);
-    const float4 ka = *reinterpret_cast<const float4*>(kq + d0), kp = *reinterpret_cast<const float4*>(kq + dp);
-    const float4 vn4 = *reinterpret_cast<const float4*>(vq + d0);
-    const float sg = d0 < 32 ? -1.f : 1.f;
-    const float4 q4 = make_float4(qa.x * c4.x + sg * qb.x * s4.x, qa.y * c4.y + sg * qb.y * s4.y, qa.z * c4.z + sg * qb.z * s4.z, qa.w * c4.w + sg * qb.w * s4.w);
-    const float4 kn4 = make_float4(ka.x * c4.x + sg * kp.x * s4.x, ka.y * c4.y + sg * kp.y * s4.y, ka.z * c4.z + sg * kp.z * s4.z, ka.w * c4.w + sg * kp.w * s4.w);
-    if (!st->done && h % gsz == 0 && wave == 0 && grp == 0) {            // KV-cache append: one wave per kv head
-        *reinterpret_cast<float4*>(kcache + ((long long)g * p.max_len + pos) * 64 + d0) = kn4;
-        *reinterpret_cast<float4*>(vcache + ((long long)g * p.max_len + pos) * 64 + d0) = vn4;
-    }
-    const float NEG = -__builtin_huge_valf();
-    float m_run = NEG, l_run = 0.f;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int d0 = sub * 4;
+    const NewToken nt = load_new_token(qkv, h, g, p.heads, p.kv_heads, p.rope_cos, p.rope_sin, pos, d0);
+    if (!st->done && h % gsz == 0 && wave == 0 && grp == 0) append_kv(kcache, vcache, g, p.max_len, pos, d0, nt.kn4, nt.vn4);   // one wave per kv head
+    SoftmaxState s;
     for (int base = 0; base < L; base += PASS) {     // workgroup-uniform
         const bool more = base + PASS < L;
         if (more) load_pass(base + PASS, kn, vn);     // longer contexts: the next pass is in flight under this pass's arithmetic
-        float sc[NS];
-        float mt = NEG;
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            const int j = base + wave * WPASS + sl * 4 + grp;
-            const float4 kk = (j == pos) ? kn4 : k4[sl];
-            float a = q4.x * kk.x + q4.y * kk.y + q4.z * kk.z + q4.w * kk.w;
-            a = group16_sum(a) * 0.125f;
-            sc[sl] = j < L ? a : NEG;
-            mt = fmaxf(mt, sc[sl]);
-        }
-        mt = fmaxf(mt, __shfl_xor(mt, 16)); mt = fmaxf(mt, __shfl_xor(mt, 32));
-        if (mt != NEG) {                             // wave-uniform: false when this wave holds no key of the pass
-            const float m_new = fmaxf(m_run, mt);
-            const float scale = (m_run == NEG) ? 0.f : expf(m_run - m_new);
-            acc.x *= scale; acc.y *= scale; acc.z *= scale; acc.w *= scale;
-            float lt = 0.f;
-#pragma unroll
-            for (int sl = 0; sl < NS; ++sl) {
-                const int j = base + wave * WPASS + sl * 4 + grp;
-                const float e = (sc[sl] == NEG) ? 0.f : expf(sc[sl] - m_new);
-                const float4 vv = (j == pos) ? vn4 : v4[sl];
-                acc.x += e * vv.x; acc.y += e * vv.y; acc.z += e * vv.z; acc.w += e * vv.w;
-                lt += e;
-            }
-            l_run = l_run * scale + lt;              // per-group partial (identical on the 16 lanes of a group)
-            m_run = m_new;
-        }
+        softmax_pass<NS, true, true>(s, nt.q4, k4, v4, base + wave * WPASS, grp, L, pos, nt.kn4, nt.vn4);
         if (more) {
 #pragma unroll
             for (int sl = 0; sl < NS; ++sl) { k4[sl] = kn[sl]; v4[sl] = vn[sl]; }
         }
     }
-    acc.x += __shfl_xor(acc.x, 16); acc.y += __shfl_xor(acc.y, 16); acc.z += __shfl_xor(acc.z, 16); acc.w += __shfl_xor(acc.w, 16);
-    acc.x += __shfl_xor(acc.x, 32); acc.y += __shfl_xor(acc.y, 32); acc.z += __shfl_xor(acc.z, 32); acc.w += __shfl_xor(acc.w, 32);
-    l_run += __shfl_xor(l_run, 16); l_run += __shfl_xor(l_run, 32);
-    if (grp == 0) *reinterpret_cast<float4*>(&pw[wave][sub * 4]) = acc;
-    if (lane == 0) { pw[wave][64] = (l_run > 0.f) ? m_run : 0.f; pw[wave][65] = l_run; }
+    wave_finish(s);
+    if (grp == 0) store_partial(pw[wave], d0, s.acc, s.m_run, s.l_run, lane == 0);
     __syncthreads();
-    if (tid < 16) {                                  // merge the waves (fixed order), normalise
-        float M = NEG;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) if (pw[ww][65] > 0.f) M = fmaxf(M, pw[ww][64]);
-        float den = 0.f; float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) {
-            const float wgt = (pw[ww][65] > 0.f) ? expf(pw[ww][64] - M) : 0.f;
-            const float4 t = *reinterpret_cast<const float4*>(&pw[ww][tid * 4]);
-            den += wgt * pw[ww][65];
-            a.x += wgt * t.x; a.y += wgt * t.y; a.z += wgt * t.z; a.w += wgt * t.w;
-        }
-        const float inv = 1.f / den;
-        *reinterpret_cast<float4*>(p.out + (long long)b * p.ldo + h * 64 + tid * 4) = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
-    }
+    if (tid < 16)                                    // merge the waves (fixed order), normalise
+        *reinterpret_cast<float4*>(p.out + (long long)b * p.ldo + h * 64 + tid * 4) = merge_rows<NW>(pw[0], ATTN_PART, tid * 4).normalised();
 }
 
 // The same attention with the heads of a kv group in ONE workgroup (round 4): workgroup = (sequence b, kv head g), 4 key waves x HS head subsets (wave = hs * 4 + kw);
@@ -796,92 +738,34 @@ static __global__ __launch_bounds__(512) void attn_decode_batch_gqa_kernel(AttnD
         }
     };
     load_pass(0);
-    const float* kq = qkv + p.heads * 64 + g * 64;
-    const float* vq = qkv + (p.heads + p.kv_heads) * 64 + g * 64;
-    const int d0 = sub * 4, dp = (d0 + 32) & 63;
-    const float4 c4 = *reinterpret_cast<const float4*>(p.rope_cos + pos * 32 + (d0 & 31));
-    const float4 s4 = *reinterpret_cast<const float4*>(p.rope_sin + pos * 32 + (d0 & 31));
-    const float4 ka = *reinterpret_cast<const float4*>(kq + d0), kp = *reinterpret_cast<const float4*>(kq + dp);
-    const float4 vn4 = *reinterpret_cast<const float4*>(vq + d0);
-    const float sg = d0 < 32 ? -1.f : 1.f;
-    const float4 kn4 = make_float4(ka.x * c4.x + sg * kp.x * s4.x, ka.y * c4.y + sg * kp.y * s4.y, ka.z * c4.z + sg * kp.z * s4.z, ka.w * c4.w + sg * kp.w * s4.w);
+    const int d0 = sub * 4;
+    const float4 kn4 = rope_row4(qkv + p.heads * 64 + g * 64, p.rope_cos, p.rope_sin, pos, d0);
+    const float4 vn4 = *reinterpret_cast<const float4*>(qkv + (p.heads + p.kv_heads) * 64 + g * 64 + d0);
     float4 q4[HPW];
 #pragma unroll
-    for (int i = 0; i < HPW; ++i) {
-        const float* qraw = qkv + (long long)(g * gsz + min(h0 + i, gsz - 1)) * 64;       // (clamped: unused entries of a short subset read a valid head)
-        const float4 qa = *reinterpret_cast<const float4*>(qraw + d0), qb = *reinterpret_cast<const float4*>(qraw + dp);
-        q4[i] = make_float4(qa.x * c4.x + sg * qb.x * s4.x, qa.y * c4.y + sg * qb.y * s4.y, qa.z * c4.z + sg * qb.z * s4.z, qa.w * c4.w + sg * qb.w * s4.w);
-    }
-    if (!st->done && wv == 0 && grp == 0) {                  // KV-cache append: one wave per workgroup
-        *reinterpret_cast<float4*>(kcache + ((long long)g * p.max_len + pos) * 64 + d0) = kn4;
-        *reinterpret_cast<float4*>(vcache + ((long long)g * p.max_len + pos) * 64 + d0) = vn4;
-    }
-    const float NEG = -__builtin_huge_valf();
-    float m_run[HPW], l_run[HPW];
-    float4 acc[HPW];
-#pragma unroll
-    for (int i = 0; i < HPW; ++i) { m_run[i] = NEG; l_run[i] = 0.f; acc[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
-    for (int base = 0; base < L; base += PASS) {     // workgroup-uniform
-        if (base > 0) load_pass(base);
+    for (int i = 0; i < HPW; ++i)                    // (clamped: unused entries of a short subset read a valid head)
+        q4[i] = rope_row4(qkv + (long long)(g * gsz + min(h0 + i, gsz - 1)) * 64, p.rope_cos, p.rope_sin, pos, d0);
+    if (!st->done && wv == 0 && grp == 0) append_kv(kcache, vcache, g, p.max_len, pos, d0, kn4, vn4);       // one wave per workgroup
+    SoftmaxState s[HPW];
+    auto heads_pass = [&](int base) {
 #pragma unroll
         for (int i = 0; i < HPW; ++i) {
             if (i >= nh) break;                      // wave-uniform
-            float sc[NS];
-            float mt = NEG;
-#pragma unroll
-            for (int sl = 0; sl < NS; ++sl) {
-                const int j = base + wave * WPASS + sl * 4 + grp;
-                const float4 kk = (j == pos) ? kn4 : k4[sl];
-                float a = q4[i].x * kk.x + q4[i].y * kk.y + q4[i].z * kk.z + q4[i].w * kk.w;
-                a = group16_sum(a) * 0.125f;
-                sc[sl] = j < L ? a : NEG;
-                mt = fmaxf(mt, sc[sl]);
-            }
-            mt = fmaxf(mt, __shfl_xor(mt, 16)); mt = fmaxf(mt, __shfl_xor(mt, 32));
-            if (mt != NEG) {                         // wave-uniform: false when this wave holds no key of the pass
-                const float m_new = fmaxf(m_run[i], mt);
-                const float scale = (m_run[i] == NEG) ? 0.f : expf(m_run[i] - m_new);
-                acc[i].x *= scale; acc[i].y *= scale; acc[i].z *= scale; acc[i].w *= scale;
-                float lt = 0.f;
-#pragma unroll
-                for (int sl = 0; sl < NS; ++sl) {
-                    const int j = base + wave * WPASS + sl * 4 + grp;
-                    const float e = (sc[sl] == NEG) ? 0.f : expf(sc[sl] - m_new);
-                    const float4 vv = (j == pos) ? vn4 : v4[sl];
-                    acc[i].x += e * vv.x; acc[i].y += e * vv.y; acc[i].z += e * vv.z; acc[i].w += e * vv.w;
-                    lt += e;
-                }
-                l_run[i] = l_run[i] * scale + lt;
-                m_run[i] = m_new;
-            }
+            softmax_pass<NS, true, true>(s[i], q4[i], k4, v4, base + wave * WPASS, grp, L, pos, kn4, vn4);
         }
-    }
+    };
+    heads_pass(0);                                   // L >= 1; its rows are in flight since load_pass(0)
+    for (int base = PASS; base < L; base += PASS) { load_pass(base); heads_pass(base); }      // workgroup-uniform
 #pragma unroll
     for (int i = 0; i < HPW; ++i) {
         if (i >= nh) break;
-        float4 a = acc[i]; float l = l_run[i];
-        a.x += __shfl_xor(a.x, 16); a.y += __shfl_xor(a.y, 16); a.z += __shfl_xor(a.z, 16); a.w += __shfl_xor(a.w, 16);
-        a.x += __shfl_xor(a.x, 32); a.y += __shfl_xor(a.y, 32); a.z += __shfl_xor(a.z, 32); a.w += __shfl_xor(a.w, 32);
-        l += __shfl_xor(l, 16); l += __shfl_xor(l, 32);
-        if (grp == 0) *reinterpret_cast<float4*>(&pw[wave][h0 + i][sub * 4]) = a;
-        if (lane == 0) { pw[wave][h0 + i][64] = (l > 0.f) ? m_run[i] : 0.f; pw[wave][h0 + i][65] = l; }
+        wave_finish(s[i]);
+        if (grp == 0) store_partial(pw[wave][h0 + i], d0, s[i].acc, s[i].m_run, s[i].l_run, lane == 0);
     }
     __syncthreads();
     if (tid < 16 * gsz) {                            // merge the key waves of every head (fixed order), normalise
         const int hh = tid >> 4, t = tid & 15;
-        float M = NEG;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) if (pw[ww][hh][65] > 0.f) M = fmaxf(M, pw[ww][hh][64]);
-        float den = 0.f; float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) {
-            const float wgt = (pw[ww][hh][65] > 0.f) ? expf(pw[ww][hh][64] - M) : 0.f;
-            const float4 tq = *reinterpret_cast<const float4*>(&pw[ww][hh][t * 4]);
-            den += wgt * pw[ww][hh][65];
-            a.x += wgt * tq.x; a.y += wgt * tq.y; a.z += wgt * tq.z; a.w += wgt * tq.w;
-        }
-        const float inv = 1.f / den;
-        *reinterpret_cast<float4*>(p.out + (long long)b * p.ldo + (g * gsz + hh) * 64 + t * 4) = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
+        *reinterpret_cast<float4*>(p.out + (long long)b * p.ldo + (g * gsz + hh) * 64 + t * 4) = merge_rows<NW>(pw[0][hh], 2 * HPW * ATTN_PART, t * 4).normalised();
     }
 }
 
@@ -943,15 +827,11 @@ static __global__ __launch_bounds__(NW * 64) void attn_decode_batch_mfma_kernel(
     float4 qf[4], kn[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int d0 = 16 * i + 4 * q, dp = (d0 + 32) & 63;
-        const float4 c4 = *reinterpret_cast<const float4*>(p.rope_cos + pos * 32 + (d0 & 31));
-        const float4 s4 = *reinterpret_cast<const float4*>(p.rope_sin + pos * 32 + (d0 & 31));
-        const float4 qa = *reinterpret_cast<const float4*>(qraw + d0), qb = *reinterpret_cast<const float4*>(qraw + dp);
-        const float4 ka = *reinterpret_cast<const float4*>(kq + d0), kp = *reinterpret_cast<const float4*>(kq + dp);
-        const float sg = d0 < 32 ? -1.f : 1.f;
+        const int d0 = 16 * i + 4 * q;
         const float qs = r < gsz ? 0.125f : 0.f;     // columns beyond the group: zero queries (scores 0, never stored)
-        qf[i] = make_float4((qa.x * c4.x + sg * qb.x * s4.x) * qs, (qa.y * c4.y + sg * qb.y * s4.y) * qs, (qa.z * c4.z + sg * qb.z * s4.z) * qs, (qa.w * c4.w + sg * qb.w * s4.w) * qs);
-        kn[i] = make_float4(ka.x * c4.x + sg * kp.x * s4.x, ka.y * c4.y + sg * kp.y * s4.y, ka.z * c4.z + sg * kp.z * s4.z, ka.w * c4.w + sg * kp.w * s4.w);
+        const float4 t = rope_row4(qraw, p.rope_cos, p.rope_sin, pos, d0);
+        qf[i] = make_float4(t.x * qs, t.y * qs, t.z * qs, t.w * qs);
+        kn[i] = rope_row4(kq, p.rope_cos, p.rope_sin, pos, d0);
     }
     const float4 vn4 = *reinterpret_cast<const float4*>(vq + 4 * r);
     if (!st->done && slice == 0 && wave == 0) {      // KV-cache append: one wave per (sequence, kv head)
@@ -1038,25 +918,9 @@ static __global__ __launch_bounds__(NW * 64) void attn_decode_batch_mfma_kernel(
     __syncthreads();
     for (int e = tid; e < 16 * gsz; e += NW * 64) {  // merge the waves of every head (fixed order)
         const int hh = e >> 4, t = e & 15;
-        float M = NEG;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) if (pw[ww][hh][65] > 0.f) M = fmaxf(M, pw[ww][hh][64]);
-        float den = 0.f; float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) {
-            const float wgt = (pw[ww][hh][65] > 0.f) ? expf(pw[ww][hh][64] - M) : 0.f;
-            const float4 tq = *reinterpret_cast<const float4*>(&pw[ww][hh][t * 4]);
-            den += wgt * pw[ww][hh][65];
-            a.x += wgt * tq.x; a.y += wgt * tq.y; a.z += wgt * tq.z; a.w += wgt * tq.w;
-        }
-        if (S == 1) {
-            const float inv = 1.f / den;
-            *reinterpret_cast<float4*>(p.out + (long long)b * p.ldo + (g * gsz + hh) * 64 + t * 4) = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
-        } else {
-            float* pr = p.part + (((long long)pair * S + slice) * gsz + hh) * ATTN_PART;
-            *reinterpret_cast<float4*>(pr + t * 4) = a;
-            if (t == 0) { pr[64] = (den > 0.f) ? M : 0.f; pr[65] = den; }
-        }
+        const Merged m = merge_rows<NW>(pw[0][hh], 16 * ATTN_PART, t * 4);
+        if (S == 1) *reinterpret_cast<float4*>(p.out + (long long)b * p.ldo + (g * gsz + hh) * 64 + t * 4) = m.normalised();
+        else store_partial(p.part + (((long long)pair * S + slice) * gsz + hh) * ATTN_PART, t * 4, m.a, m.M, m.den, t == 0);
     }
 }
 
@@ -1069,25 +933,8 @@ static __global__ __launch_bounds__(256) void attn_merge_batch_kernel(AttnDecode
     const int t = e & 15, h = (e >> 4) % p.heads, b = (e >> 4) / p.heads, g = h / gsz, hh = h % gsz;
     const float* pr = p.part + (((long long)(b * p.kv_heads + g) * S) * gsz + hh) * ATTN_PART;
     float4 pa[MAXS]; float2 ml[MAXS];
-#pragma unroll
-    for (int s = 0; s < MAXS; ++s) {                 // every partial requested before the first is used (unconditional, clamped)
-        const float* ps = pr + (long long)min(s, S - 1) * gsz * ATTN_PART;
-        pa[s] = *reinterpret_cast<const float4*>(ps + t * 4);
-        ml[s] = *reinterpret_cast<const float2*>(ps + 64);
-    }
-    const float NEG = -__builtin_huge_valf();
-    float M = NEG;
-#pragma unroll
-    for (int s = 0; s < MAXS; ++s) if (s < S && ml[s].y > 0.f) M = fmaxf(M, ml[s].x);
-    float den = 0.f; float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int s = 0; s < MAXS; ++s) {
-        const float wgt = (s < S && ml[s].y > 0.f) ? expf(ml[s].x - M) : 0.f;
-        den += wgt * ml[s].y;
-        a.x += wgt * pa[s].x; a.y += wgt * pa[s].y; a.z += wgt * pa[s].z; a.w += wgt * pa[s].w;
-    }
-    const float inv = 1.f / den;
-    *reinterpret_cast<float4*>(p.out + (long long)b * p.ldo + h * 64 + t * 4) = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
+    load_partials<MAXS>(pr, (long long)gsz * ATTN_PART, t * 4, S, ml, pa);       // every partial requested before the first is used
+    *reinterpret_cast<float4*>(p.out + (long long)b * p.ldo + h * 64 + t * 4) = merge_partials<MAXS>(S, [&](int q) { return ml[q]; }, [&](int q) { return pa[q]; }).normalised();
 }
 
 // advance the KV length of every slot after a backbone step

@@ -5,6 +5,7 @@
 // hipGraph can be replayed for every token without host involvement.
 #pragma once
 #include "common.h"
+#include "decode_attn.h"
 
 namespace cv {
 
@@ -87,8 +88,6 @@ struct GemvArgs {
     const float* opart = nullptr; int n_opart = 0; float* x_out = nullptr;
 };
 
-constexpr int ATTN_PART = 68;      // 64 unnormalised numerators + running max + denominator (+2 pad: rows stay 16-byte aligned)
-
 
 // Latency structure (batch-1 decode is a chain of ~125 short kernels, each bounded by ONE memory round trip if written so):
 // every lane first issues ALL of its weight loads (ROWS x STEPS x 16 B, non-temporal: each byte is read once per token),
@@ -124,12 +123,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_kernel(GemvArgs p) {
     float4 pa[NQ]; float2 ml[NQ];
     if constexpr (NSP > 0) {
         const int t4 = min(tid, p.K / 4 - 1);                 // thread t owns dims 4t .. 4t+3 of x (head t / 16)
-        const float* ph = p.part + (long long)(t4 >> 4) * NSP * ATTN_PART;
-#pragma unroll
-        for (int q = 0; q < NSP; ++q) {
-            pa[q] = *reinterpret_cast<const float4*>(ph + q * ATTN_PART + (t4 & 15) * 4);
-            ml[q] = *reinterpret_cast<const float2*>(ph + q * ATTN_PART + 64);
-        }
+        load_partials<NSP>(p.part + (long long)(t4 >> 4) * NSP * ATTN_PART, ATTN_PART, (t4 & 15) * 4, NSP, ml, pa);
     }
     constexpr int XR = XLDS ? STEPS / 2 : 1;                 // float4 per thread: XR * 256 of them cover K <= STEPS * WAVES * 128
     u32x4 xq[XR];                                            // (a native vector: an array of float4 that lives across order_memory() goes to scratch)
@@ -196,19 +190,9 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_kernel(GemvArgs p) {
             s_new = group16_sum(qn.x * kn.x + qn.y * kn.y + qn.z * kn.z + qn.w * kn.w) * 0.125f;
         }
         if (tid * 4 < p.K) {
-            float M = p.qnew ? s_new : ml[0].x;
-#pragma unroll
-            for (int q = 0; q < NSP; ++q) if (ml[q].y > 0.f || !p.qnew) M = fmaxf(M, ml[q].x);
-            float den = 0.f; float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int q = 0; q < NSP; ++q) {
-                const float w = (ml[q].y > 0.f) ? expf(ml[q].x - M) : 0.f;       // an empty slice carries l = 0
-                den += w * ml[q].y;
-                a.x += w * pa[q].x; a.y += w * pa[q].y; a.z += w * pa[q].z; a.w += w * pa[q].w;
-            }
-            if (p.qnew) { const float w = expf(s_new - M); den += w; a.x += w * vn.x; a.y += w * vn.y; a.z += w * vn.z; a.w += w * vn.w; }
-            const float inv = 1.f / den;
-            *reinterpret_cast<float4*>(&xs[tid * 4]) = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
+            Merged r = merge_partials<NSP>(NSP, [&](int q) { return ml[q]; }, [&](int q) { return pa[q]; }, p.qnew ? s_new : ml[0].x, !p.qnew);      // this site's own rule for the max: see merge_partials
+            if (p.qnew) { const float w = expf(s_new - r.M); r.den += w; r.a.x += w * vn.x; r.a.y += w * vn.y; r.a.z += w * vn.z; r.a.w += w * vn.w; }
+            *reinterpret_cast<float4*>(&xs[tid * 4]) = r.normalised();
         }
         __syncthreads();
 #pragma unroll
@@ -433,61 +417,16 @@ static __global__ __launch_bounds__(64) void attn_decode_kernel(AttnDecodeArgs p
         }
     };
     load_pass(kb);
-    // rotate-half RoPE in registers: lane dims d = sub*4 .. +3, partner dims (d + 32) % 64, sign - for d < 32
-    const float* qraw = p.qkv + h * 64;
-    const float* kq = p.qkv + p.heads * 64 + g * 64;
-    const float* vq = p.qkv + (p.heads + p.kv_heads) * 64 + g * 64;
-    const int d0 = sub * 4, dp = (d0 + 32) & 63;
-    const float4 c4 = *reinterpret_cast<const float4*>(p.rope_cos + pos * 32 + (d0 & 31));
-    const float4 s4 = *reinterpret_cast<const float4*>(p.rope_sin + pos * 32 + (d0 & 31));
-    const float4 qa = *reinterpret_cast<const float4*>(qraw + d0), qb = *reinterpret_cast<const float4*>(qraw + dp);
-    const float4 ka = *reinterpret_cast<const float4*>(kq + d0), kp = *reinterpret_cast<const float4*>(kq + dp);
-    const float4 vn4 = *reinterpret_cast<const float4*>(vq + d0);
-    const float sg = d0 < 32 ? -1.f : 1.f;
-    const float4 q4 = make_float4(qa.x * c4.x + sg * qb.x * s4.x, qa.y * c4.y + sg * qb.y * s4.y, qa.z * c4.z + sg * qb.z * s4.z, qa.w * c4.w + sg * qb.w * s4.w);
-    const float4 kn4 = make_float4(ka.x * c4.x + sg * kp.x * s4.x, ka.y * c4.y + sg * kp.y * s4.y, ka.z * c4.z + sg * kp.z * s4.z, ka.w * c4.w + sg * kp.w * s4.w);
-    if (!p.st->done && sp == 0 && h % gsz == 0 && grp == 0) {               // KV-cache append: one wave per kv head
-        *reinterpret_cast<float4*>(p.kcache + ((long long)g * p.max_len + pos) * 64 + d0) = kn4;
-        *reinterpret_cast<float4*>(p.vcache + ((long long)g * p.max_len + pos) * 64 + d0) = vn4;
-    }
-    const float NEG = -__builtin_huge_valf();
-    float m_run = NEG, l_run = 0.f;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int base = kb; base < ke; base += PASS) {   // wave-uniform
+    const int d0 = sub * 4;
+    const NewToken nt = load_new_token(p.qkv, h, g, p.heads, p.kv_heads, p.rope_cos, p.rope_sin, pos, d0);     // rotate-half RoPE in registers
+    if (!p.st->done && sp == 0 && h % gsz == 0 && grp == 0) append_kv(p.kcache, p.vcache, g, p.max_len, pos, d0, nt.kn4, nt.vn4);   // one wave per kv head
+    SoftmaxState s;
+    for (int base = kb; base < ke; base += PASS) {   // wave-uniform; no SKIP_EMPTY: every pass of a slice holds a key
         if (base != kb) load_pass(base);
-        float sc[NS];
-        float mt = NEG;
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            const int j = base + sl * 4 + grp;
-            const float4 kk = (j == pos) ? kn4 : k4[sl];
-            float a = q4.x * kk.x + q4.y * kk.y + q4.z * kk.z + q4.w * kk.w;
-            a = group16_sum(a) * 0.125f;
-            sc[sl] = j < ke ? a : NEG;
-            mt = fmaxf(mt, sc[sl]);
-        }
-        mt = fmaxf(mt, __shfl_xor(mt, 16)); mt = fmaxf(mt, __shfl_xor(mt, 32));
-        const float m_new = fmaxf(m_run, mt);        // finite: the pass holds at least one key
-        const float scale = (m_run == NEG) ? 0.f : expf(m_run - m_new);
-        acc.x *= scale; acc.y *= scale; acc.z *= scale; acc.w *= scale;
-        float lt = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            const int j = base + sl * 4 + grp;
-            const float e = (sc[sl] == NEG) ? 0.f : expf(sc[sl] - m_new);
-            const float4 vv = (j == pos) ? vn4 : v4[sl];
-            acc.x += e * vv.x; acc.y += e * vv.y; acc.z += e * vv.z; acc.w += e * vv.w;
-            lt += e;
-        }
-        l_run = l_run * scale + lt;                 // per-group partial (identical on the 16 lanes of a group)
-        m_run = m_new;
+        softmax_pass<NS, true, false>(s, nt.q4, k4, v4, base, grp, ke, pos, nt.kn4, nt.vn4);
     }
-    acc.x += __shfl_xor(acc.x, 16); acc.y += __shfl_xor(acc.y, 16); acc.z += __shfl_xor(acc.z, 16); acc.w += __shfl_xor(acc.w, 16);
-    acc.x += __shfl_xor(acc.x, 32); acc.y += __shfl_xor(acc.y, 32); acc.z += __shfl_xor(acc.z, 32); acc.w += __shfl_xor(acc.w, 32);
-    l_run += __shfl_xor(l_run, 16); l_run += __shfl_xor(l_run, 32);
-    float* pr = p.part + (long long)blockIdx.x * ATTN_PART;
-    if (grp == 0) *reinterpret_cast<float4*>(pr + d0) = acc;
-    if (lane == 0) { pr[64] = (l_run > 0.f) ? m_run : 0.f; pr[65] = l_run; }
+    wave_finish(s);
+    if (grp == 0) store_partial(p.part + (long long)blockIdx.x * ATTN_PART, d0, s.acc, s.m_run, s.l_run, lane == 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -547,75 +486,21 @@ __global__ __launch_bounds__(NW * 64) void attn_oproj_kernel(AttnOprojArgs p) {
     // registers less across the attention, and the K / V loads stay in flight behind the counted wait
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) wlds[it][tid] = wv[it];
-    const float* qraw = p.qkv + h * 64;
-    const float* kq = p.qkv + p.heads * 64 + g * 64;
-    const float* vq = p.qkv + (p.heads + p.kv_heads) * 64 + g * 64;
-    const int d0 = sub * 4, dp = (d0 + 32) & 63;
-    const float4 c4 = *reinterpret_cast<const float4*>(p.rope_cos + pos * 32 + (d0 & 31));
-    const float4 s4 = *reinterpret_cast<const float4*>(p.rope_sin + pos * 32 + (d0 & 31));
-    const float4 qa = *reinterpret_cast<const float4*>(qraw + d0), qb = *reinterpret_cast<const float4*>(qraw + dp);
-    const float4 ka = *reinterpret_cast<const float4*>(kq + d0), kp = *reinterpret_cast<const float4*>(kq + dp);
-    const float4 vn4 = *reinterpret_cast<const float4*>(vq + d0);
-    const float sg = d0 < 32 ? -1.f : 1.f;
-    const float4 q4 = make_float4(qa.x * c4.x + sg * qb.x * s4.x, qa.y * c4.y + sg * qb.y * s4.y, qa.z * c4.z + sg * qb.z * s4.z, qa.w * c4.w + sg * qb.w * s4.w);
-    const float4 kn4 = make_float4(ka.x * c4.x + sg * kp.x * s4.x, ka.y * c4.y + sg * kp.y * s4.y, ka.z * c4.z + sg * kp.z * s4.z, ka.w * c4.w + sg * kp.w * s4.w);
-    if (!p.st->done && wave == 0 && rb == 0 && h % gsz == 0 && grp == 0) {  // KV-cache append: one wave per kv head
-        *reinterpret_cast<float4*>(p.kcache + ((long long)g * p.max_len + pos) * 64 + d0) = kn4;
-        *reinterpret_cast<float4*>(p.vcache + ((long long)g * p.max_len + pos) * 64 + d0) = vn4;
+    const int d0 = sub * 4;
+    const NewToken nt = load_new_token(p.qkv, h, g, p.heads, p.kv_heads, p.rope_cos, p.rope_sin, pos, d0);
+    if (!p.st->done && wave == 0 && rb == 0 && h % gsz == 0 && grp == 0) append_kv(p.kcache, p.vcache, g, p.max_len, pos, d0, nt.kn4, nt.vn4);   // one wave per kv head
+    SoftmaxState s;
+    // the first pass (its rows are in flight since load_pass(kb)) stands ahead of the loop: written as `if (base != kb) load_pass(base)` inside it, the compiler keeps
+    // k4 / v4 live around the loop and <16, 2, 6> no longer fits its 128 registers
+    if (kb < ke) softmax_pass<NS, true, false>(s, nt.q4, k4, v4, kb, grp, ke, pos, nt.kn4, nt.vn4);
+    for (int base = kb + PASS; base < ke; base += PASS) {   // wave-uniform; no SKIP_EMPTY: every pass of a slice holds a key
+        load_pass(base);
+        softmax_pass<NS, true, false>(s, nt.q4, k4, v4, base, grp, ke, pos, nt.kn4, nt.vn4);
     }
-    const float NEG = -__builtin_huge_valf();
-    float m_run = NEG, l_run = 0.f;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int base = kb; base < ke; base += PASS) {   // wave-uniform
-        if (base != kb) load_pass(base);
-        float sc[NS];
-        float mt = NEG;
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            const int j = base + sl * 4 + grp;
-            const float4 kk = (j == pos) ? kn4 : k4[sl];
-            float a = q4.x * kk.x + q4.y * kk.y + q4.z * kk.z + q4.w * kk.w;
-            a = group16_sum(a) * 0.125f;
-            sc[sl] = j < ke ? a : NEG;
-            mt = fmaxf(mt, sc[sl]);
-        }
-        mt = fmaxf(mt, __shfl_xor(mt, 16)); mt = fmaxf(mt, __shfl_xor(mt, 32));
-        const float m_new = fmaxf(m_run, mt);
-        const float scale = (m_run == NEG) ? 0.f : expf(m_run - m_new);
-        acc.x *= scale; acc.y *= scale; acc.z *= scale; acc.w *= scale;
-        float lt = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            const int j = base + sl * 4 + grp;
-            const float e = (sc[sl] == NEG) ? 0.f : expf(sc[sl] - m_new);
-            const float4 vv = (j == pos) ? vn4 : v4[sl];
-            acc.x += e * vv.x; acc.y += e * vv.y; acc.z += e * vv.z; acc.w += e * vv.w;
-            lt += e;
-        }
-        l_run = l_run * scale + lt;
-        m_run = m_new;
-    }
-    acc.x += __shfl_xor(acc.x, 16); acc.y += __shfl_xor(acc.y, 16); acc.z += __shfl_xor(acc.z, 16); acc.w += __shfl_xor(acc.w, 16);
-    acc.x += __shfl_xor(acc.x, 32); acc.y += __shfl_xor(acc.y, 32); acc.z += __shfl_xor(acc.z, 32); acc.w += __shfl_xor(acc.w, 32);
-    l_run += __shfl_xor(l_run, 16); l_run += __shfl_xor(l_run, 32);
-    if (grp == 0) *reinterpret_cast<float4*>(&pw[wave][d0]) = acc;
-    if (lane == 0) { pw[wave][64] = (l_run > 0.f) ? m_run : 0.f; pw[wave][65] = l_run; }
+    wave_finish(s);
+    if (grp == 0) store_partial(pw[wave], d0, s.acc, s.m_run, s.l_run, lane == 0);
     __syncthreads();
-    if (tid < 16) {                                  // flash-decoding merge of the NW slices (fixed order), normalised: a_h
-        float M = NEG;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) if (pw[w][65] > 0.f) M = fmaxf(M, pw[w][64]);
-        float den = 0.f; float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const float wgt = (pw[w][65] > 0.f) ? expf(pw[w][64] - M) : 0.f;
-            const float4 t = *reinterpret_cast<const float4*>(&pw[w][tid * 4]);
-            den += wgt * pw[w][65];
-            a.x += wgt * t.x; a.y += wgt * t.y; a.z += wgt * t.z; a.w += wgt * t.w;
-        }
-        const float inv = 1.f / den;
-        *reinterpret_cast<float4*>(&as[tid * 4]) = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
-    }
+    if (tid < 16) *reinterpret_cast<float4*>(&as[tid * 4]) = merge_rows<NW>(pw[0], ATTN_PART, tid * 4).normalised();   // flash-decoding merge of the NW slices (fixed order): a_h
     __syncthreads();
     const float4 xa = *reinterpret_cast<const float4*>(&as[sub8 * 8]), xb = *reinterpret_cast<const float4*>(&as[sub8 * 8 + 4]);
     float* out = p.opart + (long long)h * p.hidden;
@@ -758,60 +643,19 @@ __global__ __launch_bounds__(256) void qkv_attn_kernel(QkvAttnArgs p) {
     __syncthreads();
     // 6. attention of this wave over its share of the slice
     const float4 q4 = *reinterpret_cast<const float4*>(&rot[sub * 4]);
-    const float NEG = -__builtin_huge_valf();
-    float m_run = NEG, l_run = 0.f;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);             // NEWTOK = false: the new token's k / v are never read
+    SoftmaxState s;
     for (int base = kb; base < ke; base += PASS) {      // workgroup-uniform
         if (base != kb) load_pass(base);
-        float sc[NS];
-        float mt = NEG;
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            const int j = base + wave * WPASS + sl * 4 + grp;
-            const float4 kk = k4[sl];
-            float a = q4.x * kk.x + q4.y * kk.y + q4.z * kk.z + q4.w * kk.w;
-            a = group16_sum(a) * 0.125f;
-            sc[sl] = j < ke ? a : NEG;
-            mt = fmaxf(mt, sc[sl]);
-        }
-        mt = fmaxf(mt, __shfl_xor(mt, 16)); mt = fmaxf(mt, __shfl_xor(mt, 32));
-        if (mt == NEG) continue;                         // wave-uniform: this wave holds no key of the pass
-        const float m_new = fmaxf(m_run, mt);
-        const float scale = (m_run == NEG) ? 0.f : expf(m_run - m_new);
-        acc.x *= scale; acc.y *= scale; acc.z *= scale; acc.w *= scale;
-        float lt = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            const float e = (sc[sl] == NEG) ? 0.f : expf(sc[sl] - m_new);
-            const float4 vv = v4[sl];
-            acc.x += e * vv.x; acc.y += e * vv.y; acc.z += e * vv.z; acc.w += e * vv.w;
-            lt += e;
-        }
-        l_run = l_run * scale + lt;                     // per-group partial (identical on the 16 lanes of a group)
-        m_run = m_new;
+        softmax_pass<NS, false, true>(s, q4, k4, v4, base + wave * WPASS, grp, ke, pos, none, none);
     }
-    acc.x += __shfl_xor(acc.x, 16); acc.y += __shfl_xor(acc.y, 16); acc.z += __shfl_xor(acc.z, 16); acc.w += __shfl_xor(acc.w, 16);
-    acc.x += __shfl_xor(acc.x, 32); acc.y += __shfl_xor(acc.y, 32); acc.z += __shfl_xor(acc.z, 32); acc.w += __shfl_xor(acc.w, 32);
-    l_run += __shfl_xor(l_run, 16); l_run += __shfl_xor(l_run, 32);
+    wave_finish(s);
     // 7. merge the 4 waves (fixed order) and leave one partial per (head, slice)
-    if (grp == 0) *reinterpret_cast<float4*>(&pw[wave][sub * 4]) = acc;
-    if (lane == 0) { pw[wave][64] = (l_run > 0.f) ? m_run : 0.f; pw[wave][65] = l_run; }
+    if (grp == 0) store_partial(pw[wave], sub * 4, s.acc, s.m_run, s.l_run, lane == 0);
     __syncthreads();
     if (tid < 16) {
-        float M = NEG;
-#pragma unroll
-        for (int ww = 0; ww < 4; ++ww) if (pw[ww][65] > 0.f) M = fmaxf(M, pw[ww][64]);
-        float den = 0.f; float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int ww = 0; ww < 4; ++ww) {
-            const float wgt = (pw[ww][65] > 0.f) ? expf(pw[ww][64] - M) : 0.f;
-            const float4 t = *reinterpret_cast<const float4*>(&pw[ww][tid * 4]);
-            den += wgt * pw[ww][65];
-            a.x += wgt * t.x; a.y += wgt * t.y; a.z += wgt * t.z; a.w += wgt * t.w;
-        }
-        float* pr = p.part + (long long)blockIdx.x * ATTN_PART;
-        *reinterpret_cast<float4*>(pr + tid * 4) = a;
-        if (tid == 0) { pr[64] = den > 0.f ? M : 0.f; pr[65] = den; }
+        const Merged r = merge_rows<4>(pw[0], ATTN_PART, tid * 4);
+        store_partial(p.part + (long long)blockIdx.x * ATTN_PART, tid * 4, r.a, r.M, r.den, tid == 0);
     }
 }
 

@@ -5,7 +5,10 @@ CV_DOWN_XLDS=0 at handle creation restores the form in which every 16-lane group
 values into the same FMAs in the same order, so logits are compared bit for bit.  The branch is taken from inter = 1024 (8 k-steps) up; the tiny model
 of the other LM tests (inter = 256) never reaches it.
 
-There is no read-back of the KV cache in the C API: the cache rows are covered through the logits of the later steps, which attend over them."""
+There is no read-back of the KV cache in the C API: the cache rows are covered through the logits of the later steps, which attend over them.
+
+Second part: the decode attention (csrc/decode_attn.h, shared by the kernels of llm_kernels.h and llm_batch_kernels.h) walked across the exact edge of a wave pass."""
+import ctypes as C
 import dataclasses
 
 import pytest
@@ -76,3 +79,65 @@ def test_down_xlds_greedy_tokens(lib, models, monkeypatch, inter, use_graph):
     cfg, sd, u, want, _ = models[inter]
     lm = _lm(monkeypatch, lib, sd, cfg, True, decode_chunk=5, use_graph=use_graph)
     assert list(lm.inference(**_kw(u), max_token_text_ratio=2, min_token_text_ratio=2)) == want
+
+
+# ---- the decode attention at the edge of a pass.  A wave of attn_decode_kernel takes 48 keys per pass (12 slots x 4 lane groups), a workgroup of the batched VALU
+# form 4 x 48 = 192, the MFMA form 16-key tiles.  Three decode steps from a context of 48 * slices - 1: the new token sits at index 48 * slices - 1 (every slice one
+# full pass), then 48 * slices and 48 * slices + 1 (slices of 52 keys: a full pass and a second one that holds 1 - 4 keys; the last slice is short).
+PASS = 48
+EDGE_STEPS = 3
+
+
+@pytest.fixture(scope="module")
+def edge():
+    """(cfg, state dict, {start context: [(request, oracle tokens, oracle log-probabilities), ..]}): three requests at 191 (the batch; the first also alone), one at 383."""
+    cfg = W.tiny()[0]
+    sd = W.make_llm(cfg)
+    out = {}
+    for start, seeds in ((4 * PASS - 1, (34, 35, 36)), (8 * PASS - 1, (35,))):       # (seeds whose oracle run does not stop on a special id within the walk)
+        out[start] = []
+        for seed in seeds:
+            u = W.synthetic_utterance(cfg, W.tiny()[1], n_prompt_tok=start - 7, n_prompt_text=2, n_text=EDGE_STEPS, seed=seed)     # rows: sos + 2 + 3 + task id + prompt tokens
+            trace = {}
+            want = OL.inference(sd, cfg, u["text"], u["prompt_text"], u["llm_prompt_speech_token"], max_token_text_ratio=2, min_token_text_ratio=1, trace=trace)
+            assert len(want) >= EDGE_STEPS
+            out[start].append((u, want, trace["logp"]))
+    return cfg, sd, out
+
+
+@pytest.mark.parametrize("splits", [4, 8])
+def test_attention_pass_boundary_single_sequence(lib, edge, splits):
+    cfg, sd, reqs = edge
+    start = splits * PASS - 1
+    u, want, logp = reqs[start][0]
+    lm = Qwen2LM(sd, cfg, lib=lib, max_len=512, sampling="greedy", attn_splits=splits)
+    x = lm.build_lm_input(u["text"], u["prompt_text"], u["llm_prompt_speech_token"])
+    assert x.shape[0] == start
+    lm.prefill(x)
+    sp = lm.make_sampling(EDGE_STEPS, 2 * EDGE_STEPS)
+    for i in range(EDGE_STEPS):                                        # the new token at index start + i
+        toks, _fin = lm.decode(1, sp)
+        assert toks == [want[i]], (splits, i)
+        torch.testing.assert_close(lm.last_logits().log_softmax(-1), logp[i], rtol=1e-4, atol=1e-4)
+
+
+@pytest.mark.parametrize("form", [0, 1])
+def test_attention_pass_boundary_batch(lib, edge, form):
+    """Three lock-step slots at 191 -> 193, the per-head VALU form (0) and the MFMA form (1) pinned."""
+    cfg, sd, reqs = edge
+    start, nb = 4 * PASS - 1, 3
+    lm = Qwen2LM(sd, cfg, lib=lib, max_len=256, sampling="greedy", decode_chunk=1)
+    lib.cv_llm_set_option(lm._h, b"batch_attn", C.c_int32(form))
+    st = None
+    lib.cv_llm_batch_begin(lm._h, C.c_int32(nb), st)
+    inputs = [lm.build_lm_input(u["text"], u["prompt_text"], u["llm_prompt_speech_token"]) for u, _, _ in reqs[start]]
+    assert [x.shape[0] for x in inputs] == [start] * nb
+    lm._prefill_slots(list(range(nb)), inputs, [lm.make_sampling(EDGE_STEPS, 2 * EDGE_STEPS) for _ in range(nb)], st)
+    logits = torch.empty(cfg.speech_token_size + cfg.n_special, dtype=torch.float32)
+    for i in range(EDGE_STEPS):
+        buf, n_out, f = (C.c_int32 * nb)(), (C.c_int32 * nb)(), (C.c_int32 * nb)()
+        lib.cv_llm_batch_decode(lm._h, C.c_int32(1), buf, n_out, f, st)
+        for b, (_, want, logp) in enumerate(reqs[start]):
+            assert n_out[b] == 1 and buf[b] == want[i], (form, i, b)
+            lib.cv_llm_batch_logits(lm._h, C.c_int32(b), C.c_void_p(logits.data_ptr()), st)
+            torch.testing.assert_close(logits.log_softmax(-1), logp[i], rtol=1e-4, atol=1e-4)
