@@ -10,12 +10,14 @@
 #include <tuple>
 #include <cmath>
 #include <cstdlib>
+#include <atomic>
 #include "ops.h"
 #include "tensor_map.h"
 #include "options.h"
 #include "flow_kernels.h"
 #include "flow_fused.h"
 #include "flow_attn32.h"
+#include "flow_attn_cached.h"
 #include "flow_big.h"
 #ifdef CV_BUILD_EXPERIMENTS
 #include "experiments/flow_tail.h"      // measured no-go (profiles/r3_flow_tail_ab.txt): built, and its option accepted, only with -DCV_BUILD_EXPERIMENTS
@@ -153,6 +155,11 @@ struct cv_flow {
     long long rule_rows = 0;           // rows of the whole pass while its halves run as two chains (band_rows_for sees what the chip holds, not one chain's share)
     hipStream_t side_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<float> host_t;
+    // Incremental streaming (cv_flow_stream_*): the state of a request lives in its cv_flow_stream; the handle holds what every stream of it shares - the staging rows of
+    // the halo convolutions, the partials of the sliced attention (flow_attn_cached.h) - and the counters behind the stats "stream_cache_bytes" / "stream_chunks".
+    DevBuf s_stg, ac_m, ac_l, ac_o;
+    int stream_slices = 0;             // cv_flow_stream_slices: key slices of attn_cached_kernel, 1 .. 8; 0 = by the key count (stream_slices_for)
+    std::atomic<long long> stream_cache_bytes{0}, stream_chunks{0}, open_streams{0};       // (a stream may be closed from another thread than the one that runs chunks)
     ~cv_flow() {
         for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -884,6 +891,124 @@ static void estimator_forward(cv_flow* m, int T, int t_row, int t_rows_total, bo
     conv_cl(m->final_proj, xb, T, T, nz, 0, 1, m->s_out.as<float>() + r0 * c.mel, ACT_NONE, 0.f, nullptr, s);
 }
 
+// ---- incremental streaming pass (cv_flow_stream_*) ------------------------------------------------------------------------------------------------------------------
+// With streaming = 1 the estimator is chunk-causal: every CausalConv1d above reads two rows to the left, every attention is MASK_CHUNK with full left context, and
+// everything else is per frame.  A frame's whole Euler trajectory therefore depends on the frames up to the end of its own chunk alone, and a call that brings new
+// chunks needs from the earlier ones only (a) the K and V rows of every transformer block and (b) the two rows in front of every kernel-3 convolution - per Euler step
+// and per guidance row.  A cv_flow_stream keeps exactly that; estimator_forward_inc is estimator_forward over the NEW rows with the small-pass operators.
+// The reference has no counterpart: CosyVoice2Model.token2wav re-runs flow.inference over all tokens at every hop (cli/model.py:292-303).
+struct cv_flow_stream {
+    cv_flow* owner = nullptr;
+    int max_frames = 0, cap = 0;       // frames the caches may / do hold (chunk multiples)
+    int frames_done = 0;               // frames returned so far = rows in the caches
+    int mel_len1 = -1, n_steps = 0, calls = 0;
+    bool bf16 = false;                 // cache rows: bf16 (the fused bf16 pipeline) | fp32
+    void* kv = nullptr; size_t kv_bytes = 0;          // [step][block][guidance row][K | V][cap][inner]
+    DevBuf halo;                       // [step][convolution][guidance row][2][Kmax] fp32
+};
+
+static void stream_release(cv_flow_stream* S) {
+    std::lock_guard<std::recursive_mutex> lk(runtime_lock());
+    if (S->kv) (void)hipFree(S->kv);
+    if (S->owner) { S->owner->stream_cache_bytes -= (long long)(S->kv_bytes + S->halo.bytes); --S->owner->open_streams; }
+    S->kv = nullptr; S->kv_bytes = 0; S->owner = nullptr;
+}
+
+// Key slices of the cached attention by the key count of the call (a fixed rule: a request's bits depend on nothing else).  Measured on MI355X, bf16 mode, ms per
+// chunk of a 750-token request with 1 / 2 / 4 / 8 slices (profiles/flow_incremental.txt): 200 keys 29.0 / 28.6 / 28.2 / 29.4, 500 keys 37.5 / 34.2 / 32.0 / 32.8,
+// 900 keys 49.9 / 42.3 / 37.1 / 36.1, 1500 keys 64.4 / 48.4 / 39.9 / 38.1 - four slices from four 64-key tiles on, eight from fourteen; below four tiles one slice
+// (no merge launch).
+static int stream_slices_for(const cv_flow* m, int keys) {
+    if (m->stream_slices > 0) return m->stream_slices;
+    const int nt = (keys + 63) / 64;
+    return nt >= 14 ? 8 : nt >= 4 ? 4 : 1;
+}
+
+static void attn_cached_launch(const AttnCachedArgs& a, bool bf, hipStream_t s) {
+    const dim3 g((unsigned)(((a.Tn + 63) / 64) * a.ns), (unsigned)a.H, (unsigned)a.B);
+    if (bf) hipLaunchKernelGGL(attn_cached_kernel<true>, g, dim3(256), 0, s, a); else hipLaunchKernelGGL(attn_cached_kernel<false>, g, dim3(256), 0, s, a);
+    if (a.ns == 1) return;
+    const dim3 gm(nblk((long long)a.B * a.H * a.Tn * 16));
+    if (bf) hipLaunchKernelGGL(attn_cached_merge_kernel<true>, gm, dim3(256), 0, s, a); else hipLaunchKernelGGL(attn_cached_merge_kernel<false>, gm, dim3(256), 0, s, a);
+}
+
+// estimator_forward for the rows [T0, T0 + Tn) of Euler step `st` of stream S (both guidance rows; s_in holds their packed input, the result lands in s_out [2][Tn][mel]).
+static void estimator_forward_inc(cv_flow* m, cv_flow_stream* S, int Tn, int T0, int st, hipStream_t s) {
+    const auto& c = m->cfg; const int C = c.est_ch, H = c.est_heads, inner = H * 64, nz = 2; const long long R = (long long)nz * Tn;
+    float* pp[2] = {m->s_a.as<float>(), m->s_c.as<float>()};
+    float* xb = m->s_b.as<float>(); float* skip = m->s_skip.as<float>(); float* cat = m->s_cat.as<float>(); float* stg = m->s_stg.as<float>();
+    const bool fused = S->bf16;
+    const int nst = (int)m->stages.size(), nconv = 2 * nst + 3, Kmax = std::max(4 * c.mel, 2 * C), nblocks = nst * c.est_blocks;
+    const size_t esz = S->bf16 ? 2 : 4, slab = (size_t)S->cap * inner * esz;
+    // a kernel-3 CausalConv1d: its two left rows come from the halo of (step, convolution), its last two input rows go there for the next call
+    auto hconv = [&](const Lin& l, const float* in, int ci, float* out) {
+        float* hs = S->halo.as<float>() + ((size_t)st * nconv + ci) * nz * 2 * Kmax;
+        hipLaunchKernelGGL(halo_stage_kernel, dim3(nblk((long long)nz * (Tn + 2) * l.K)), dim3(256), 0, s, in, hs, stg, nz, Tn, l.K);
+        conv_cl(l, stg, Tn + 2, Tn, nz, 0, 1, out, ACT_NONE, 0.f, nullptr, s);
+    };
+    const float* cur = m->s_in.as<float>();
+    int flip = 0;
+    for (int si = 0; si < nst; ++si) {
+        const StageW& sw = m->stages[si];
+        const float* tm = m->t_mlp.as<float>() + ((size_t)si * S->n_steps + st) * C;
+        float* x = pp[flip];
+        hconv(sw.res.conv1, cur, 2 * si, x);
+        ln_rows(sw.res.ln1, x, xb, R, C, 1e-5f, s, ACT_MISH, 1.f, tm, R);
+        hconv(sw.res.conv2, xb, 2 * si + 1, x);
+        ln_rows(sw.res.ln2, x, xb, R, C, 1e-5f, s, ACT_MISH);
+        conv_cl(sw.res.res, cur, Tn, Tn, nz, 0, 1, x, ACT_NONE, 0.f, xb, s);
+        for (size_t ti = 0; ti < sw.tf.size(); ++ti) {     // stage_blocks' five-launch forms; K | V rows go to the caches, the attention reads them there
+            const TBlockW& t = sw.tf[ti];
+            AttnCachedArgs a{};
+            for (int b = 0; b < nz; ++b) {
+                const char* base = static_cast<const char*>(S->kv) + ((((size_t)st * nblocks + (size_t)si * c.est_blocks + ti) * nz + b) * 2) * slab;
+                a.k[b] = base; a.v[b] = base + slab; a.klen[b] = T0 + Tn;
+            }
+            a.ldc = inner; a.B = nz; a.H = H; a.Tn = Tn; a.q0 = T0; a.chunk = 2 * c.chunk; a.scale = 0.125f;
+            a.ns = stream_slices_for(m, T0 + Tn); a.pm = m->ac_m.as<float>(); a.pl = m->ac_l.as<float>(); a.po = m->ac_o.as<float>();
+            if (fused) {
+                bf16_t* qkv16 = m->s_qkv.as<bf16_t>(); bf16_t* ab = m->h_att.as<bf16_t>(); bf16_t* fb = m->h_ff.as<bf16_t>();
+                ln_gemm_bf16(t.qkv, &t.norm1, 1e-5f, x, (int)R, ACT_NONE, qkv16, 3 * inner, 3 * inner, nullptr, 0, 0, 0, s);
+                hipLaunchKernelGGL(kv_append_kernel<bf16_t>, dim3(nblk(R * 2 * inner / 8)), dim3(256), 0, s, qkv16, a, nz, Tn, T0, inner);
+                a.q = qkv16; a.ldq = 3 * inner; a.o = ab; a.ldo = inner;
+                attn_cached_launch(a, true, s);
+                gemm_bf16_res(t.out, ab, inner, (int)R, x, x, s);
+                ln_gemm_bf16(t.ff1, &t.norm3, 1e-5f, x, (int)R, ACT_GELU_ERF, fb, 4 * C, 4 * C, nullptr, 0, 0, 0, s);
+                gemm_bf16_res(t.ff2, fb, 4 * C, (int)R, x, x, s);
+                continue;
+            }
+            float* n = m->s_n.as<float>(); float* qkv = m->s_qkv.as<float>(); float* att = m->s_att.as<float>(); float* ff = m->s_ff.as<float>();
+            ln_rows(t.norm1, x, n, R, C, 1e-5f, s);
+            lin_cl(t.qkv, n, R, qkv, ACT_NONE, nullptr, s);
+            hipLaunchKernelGGL(kv_append_kernel<float>, dim3(nblk(R * 2 * inner / 4)), dim3(256), 0, s, qkv, a, nz, Tn, T0, inner);
+            a.q = qkv; a.ldq = 3 * inner; a.o = att; a.ldo = inner;
+            attn_cached_launch(a, false, s);
+            lin_cl(t.out, att, R, x, ACT_NONE, x, s);
+            ln_rows(t.norm3, x, n, R, C, 1e-5f, s);
+            lin_cl(t.ff1, n, R, ff, ACT_GELU_ERF, nullptr, s);
+            lin_cl(t.ff2, ff, R, x, ACT_NONE, x, s);
+        }
+        flip ^= 1;
+        if (si == 0) {
+            CV_HIP(hipMemcpyAsync(skip, x, (size_t)R * C * 4, hipMemcpyDeviceToDevice, s));
+            hconv(m->down_conv, x, 2 * nst, pp[flip]);
+            cur = pp[flip]; flip ^= 1;
+        } else if (si == nst - 2) {
+            hipLaunchKernelGGL(concat_cols_kernel, dim3(nblk(R * 2 * C)), dim3(256), 0, s, x, C, skip, C, cat, R);
+            cur = cat;
+        } else if (si == nst - 1) {
+            hconv(m->up_conv, x, 2 * nst + 1, pp[flip]);
+            cur = pp[flip]; flip ^= 1;
+        } else {
+            cur = x;
+        }
+    }
+    float* y = pp[flip];
+    hconv(m->final_conv, cur, 2 * nst + 2, y);
+    ln_rows(m->final_ln, y, xb, R, C, 1e-5f, s, ACT_MISH);
+    conv_cl(m->final_proj, xb, Tn, Tn, nz, 0, 1, m->s_out.as<float>(), ACT_NONE, 0.f, nullptr, s);
+}
+
 // ---- ConditionalDecoder of CosyVoice-300M (cfg.estimator == 2; flow/decoder.py:88-291 over matcha's Block1D / ResnetBlock1D / Downsample1D / Upsample1D) ------------
 // The same stage as above with three differences: the convolutions are centred (pad 1 on both sides), a Block1D normalises with GroupNorm(8) over (channels of the
 // group x TIME) instead of a LayerNorm per frame, and the stream changes resolution (stride-2 convolution down, transposed convolution up, cut to the skip's length).
@@ -1131,13 +1256,10 @@ static void dit_front(cv_flow* m, const float* tok_emb, int n_enc, const float* 
 // ---- solve_euler + inference -------------------------------------------------------------------------------------------
 // nu utterances of the same length solved together (x, mu, cond [nu][T][mel], spk [nu][mel]): the estimator sees 2 * nu batch rows, every GEMM
 // of a step runs once over all of them (same arithmetic per row as nu separate solves: rows never mix outside their own attention / conv window)
-static void solve_euler(cv_flow* m, float* x /*[nu][T][mel] in/out*/, const float* mu, const float* spk, const float* cond, int T,
-                        int n_steps, int streaming, hipStream_t s, int nu = 1) {
-    const auto& c = m->cfg;
-    const bool dit = c.estimator == 1;
-    if (dit) { dit_reserve(m, T, 2 * nu); dit_time_reserve(m, n_steps); } else { est_reserve(m, T, 2 * nu); time_reserve(m, n_steps); }
-    // cosine schedule and the t / dt recurrences of solve_euler, in fp32 like torch (flow_matching.py:89-122, 223-226)
-    std::vector<float> span(n_steps + 1), tv(n_steps), dts(n_steps);
+// cosine schedule and the t / dt recurrences of solve_euler, in fp32 like torch (flow_matching.py:89-122, 223-226)
+static void euler_schedule(int n_steps, std::vector<float>& tv, std::vector<float>& dts) {
+    std::vector<float> span(n_steps + 1);
+    tv.assign(n_steps, 0.f); dts.assign(n_steps, 0.f);
     for (int i = 0; i <= n_steps; ++i) {
         const float lin = n_steps == 0 ? 0.f : (float)i / (float)n_steps;      // torch.linspace(0, 1, n+1)
         span[i] = 1.f - cosf(lin * 0.5f * 3.14159265358979323846f);
@@ -1148,6 +1270,15 @@ static void solve_euler(cv_flow* m, float* x /*[nu][T][mel] in/out*/, const floa
         t = t + dt;
         if (st < n_steps) dt = span[st + 1] - t;
     }
+}
+
+static void solve_euler(cv_flow* m, float* x /*[nu][T][mel] in/out*/, const float* mu, const float* spk, const float* cond, int T,
+                        int n_steps, int streaming, hipStream_t s, int nu = 1) {
+    const auto& c = m->cfg;
+    const bool dit = c.estimator == 1;
+    if (dit) { dit_reserve(m, T, 2 * nu); dit_time_reserve(m, n_steps); } else { est_reserve(m, T, 2 * nu); time_reserve(m, n_steps); }
+    std::vector<float> tv, dts;
+    euler_schedule(n_steps, tv, dts);
     m->host_t = tv;                           // kept alive for the async copy
     CV_HIP(hipMemcpyAsync(m->t_val.p, m->host_t.data(), (size_t)n_steps * 4, hipMemcpyHostToDevice, s));
     const long long n = (long long)nu * T * c.mel;
@@ -1222,6 +1353,9 @@ int cv_flow_get_stat(cv_flow* m, const char* name, int64_t* value) {
         CV_CHECK(m && name && value, "null argument");
         if (std::string(name) == "graph_captures") *value = m->graph_captures;
         else if (std::string(name) == "graphs_cached") *value = (int64_t)m->graphs.size();
+        else if (std::string(name) == "stream_cache_bytes") *value = m->stream_cache_bytes.load();      // device bytes held by the open cv_flow_streams of this handle
+        else if (std::string(name) == "stream_chunks") *value = m->stream_chunks.load();                // cv_flow_stream_chunk calls served so far
+        else if (std::string(name) == "open_streams") *value = m->open_streams.load();
         else if (std::string(name).rfind("attn_phase_", 0) == 0 || std::string(name).rfind("gemm_phase_", 0) == 0) {
             // dev tool: mean shader clocks between stamps k and k + 1 of the LAST stamped launch over its workgroups (up to 65536); k = 7: workgroups,
             // k = 8: first start -> last end, k = 9: mean start offset of a workgroup after the first one, k = 10: mean end offset
@@ -1351,6 +1485,19 @@ int cv_flow_estimator_masked(cv_flow* m, const float* x, const float* mask, cons
     return guarded([&] { flow_estimator_call(m, x, mask, key_len, mu, t, spks, cond, T, streaming, out, stream); });
 }
 
+// the glue buffers of cv_flow_inference* / cv_flow_stream_chunk for nu utterances of n_tok tokens
+static void inf_reserve(cv_flow* m, int n_tok, int nu) {
+    const auto& c = m->cfg; const int d = c.dim;
+    if (n_tok > m->inf_cap || (long long)n_tok * nu > m->inf_rows) {        // per-utterance buffers follow n_tok, the stacked ones n_tok * nu
+        drop_graphs(m);
+        const size_t tk = (size_t)std::max(n_tok, m->inf_cap), rows = std::max((size_t)n_tok * nu, (size_t)m->inf_rows);
+        m->f_tok.ensure(rows * d * 4); m->f_h.ensure(2 * rows * d * 4);          // stacked: the encoder takes all utterances of a pass at once
+        m->f_mu.ensure(2 * rows * c.mel * 4); m->f_cond.ensure(2 * rows * c.mel * 4); m->f_x.ensure(2 * rows * c.mel * 4);
+        m->f_spk.ensure((size_t)8 * c.mel * 4); m->f_spkn.ensure((size_t)c.spk_dim * 4);
+        m->inf_cap = (int)tk; m->inf_rows = (long long)rows;
+    }
+}
+
 // nu utterances with the SAME token count and prompt length through one flow pass: x-vector projection, token embedding and encoder per utterance
 // (the encoder is ~8 % of the stage), the CFM Euler solve over all of them at once.  token_ids [nu][n_tok], prompt_feat [nu][mel_len1][mel],
 // embedding [nu][spk_dim], mel_out [nu][mel][T - mel_len1].  nu = 1 is cv_flow_inference.
@@ -1367,14 +1514,7 @@ static void flow_inference(cv_flow* m, int nu, const int32_t* token_ids, int n_t
     const int T = 2 * n_enc, mel_len2 = T - mel_len1;
     CV_CHECK(mel_len2 > 0 && mel_len1 >= 0, "cv_flow_inference: prompt longer than the sequence");
     CV_CHECK(nu >= 1 && nu <= 8, "cv_flow_inference_batch: 1..8 utterances");
-    if (n_tok > m->inf_cap || (long long)n_tok * nu > m->inf_rows) {        // per-utterance buffers follow n_tok, the stacked ones n_tok * nu
-        drop_graphs(m);
-        const size_t tk = (size_t)std::max(n_tok, m->inf_cap), rows = std::max((size_t)n_tok * nu, (size_t)m->inf_rows);
-        m->f_tok.ensure(rows * d * 4); m->f_h.ensure(2 * rows * d * 4);          // stacked: the encoder takes all utterances of a pass at once
-        m->f_mu.ensure(2 * rows * c.mel * 4); m->f_cond.ensure(2 * rows * c.mel * 4); m->f_x.ensure(2 * rows * c.mel * 4);
-        m->f_spk.ensure((size_t)8 * c.mel * 4); m->f_spkn.ensure((size_t)c.spk_dim * 4);
-        m->inf_cap = (int)tk; m->inf_rows = (long long)rows;
-    }
+    inf_reserve(m, n_tok, nu);
     const size_t per = (size_t)T * c.mel;
     // the conformer encoder over all utterances at once (rows stacked; its attention per utterance): same arithmetic per row as the loop below, 1/nu of the launches
     const bool enc_together = nu > 1 && c.estimator != 1 && m->enc_batch;
@@ -1537,6 +1677,145 @@ int cv_flow_inference_batch(cv_flow* m, int32_t n_utt, const int32_t* token_ids,
     return guarded([&] {
         CV_CHECK(m && m->finalized && token_ids && embedding && noise_cl && mel_out && mel_len2_out, "cv_flow_inference_batch: bad arguments");
         flow_inference(m, n_utt, token_ids, n_tok, prompt_feat, mel_len1, embedding, noise_cl, streaming, finalize, n_timesteps, mel_out, mel_len2_out, stream);
+    });
+}
+
+static void flow_stream_chunk(cv_flow* m, cv_flow_stream* S, const int32_t* token_ids, int n_tok, const float* prompt_feat, int mel_len1, const float* embedding,
+                              const float* noise_cl, int n_timesteps, float* mel_out, int32_t* n_new, void* stream) {
+    CV_CHECK(m && m->finalized && S && token_ids && embedding && noise_cl && mel_out && n_new, "cv_flow_stream_chunk: bad arguments");
+    CV_CHECK(S->owner == m, "cv_flow_stream_chunk: the stream was opened on another handle (or is closed)");
+    const auto& c = m->cfg; const int d = c.dim, C = c.est_ch, inner = c.est_heads * 64, ch = 2 * c.chunk;
+    const int n_enc = n_tok - c.pre_lookahead, T1 = 2 * n_enc, T0 = S->frames_done, Tn = T1 - T0;
+    CV_CHECK(n_enc > 0 && n_timesteps > 0 && mel_len1 >= 0, "cv_flow_stream_chunk: too few tokens");
+    CV_CHECK(T1 % ch == 0, "cv_flow_stream_chunk: misaligned frame count - 2 (n_tok - pre_lookahead) = " + std::to_string(T1) + " is not a multiple of the " + std::to_string(ch) + "-frame chunk");
+    CV_CHECK(T1 > T0, "cv_flow_stream_chunk: no new chunk - " + std::to_string(T1) + " frames, " + std::to_string(T0) + " already returned");
+    const bool first = S->calls == 0;
+    const bool bf = m->bf16_mfma != 0;
+    if (first) CV_CHECK(T1 > mel_len1, "cv_flow_stream_chunk: prompt longer than the sequence");
+    else {
+        CV_CHECK(mel_len1 == S->mel_len1, "cv_flow_stream_chunk: mel_len1 changed (" + std::to_string(S->mel_len1) + " on the stream's first call, " + std::to_string(mel_len1) + " now)");
+        CV_CHECK(n_timesteps == S->n_steps, "cv_flow_stream_chunk: n_timesteps changed (" + std::to_string(S->n_steps) + " on the stream's first call, " + std::to_string(n_timesteps) + " now)");
+        CV_CHECK(bf == S->bf16, "cv_flow_stream_chunk: the precision mode changed since the stream's first call");
+    }
+    CV_CHECK(!bf || (m->fused && C <= 256 && m->wbf16), "cv_flow_stream_chunk: bf16 mode needs the fused pipeline (option fused = 1, bf16 weights, est_ch <= 256)");
+    CV_CHECK(T1 <= S->max_frames, "cv_flow_stream_chunk: " + std::to_string(T1) + " frames pass the stream's max_frames = " + std::to_string(S->max_frames));
+    FlowScope scope(m);
+    hipStream_t s = resolve(m, stream);
+    void* stream_r = reinterpret_cast<void*>(s);
+    const int nst = (int)m->stages.size(), nconv = 2 * nst + 3, Kmax = std::max(4 * c.mel, 2 * C);
+    const size_t esz = bf ? 2 : 4, nslab = (size_t)n_timesteps * nst * c.est_blocks * 2 * 2;
+    if (first) {
+        S->mel_len1 = mel_len1; S->n_steps = n_timesteps; S->bf16 = bf;
+        const size_t before = S->halo.bytes;
+        S->halo.ensure((size_t)n_timesteps * nconv * 2 * 2 * Kmax * 4);
+        m->stream_cache_bytes += (long long)(S->halo.bytes - before);
+        CV_HIP(hipMemsetAsync(S->halo.p, 0, S->halo.bytes, s));       // the causal zero padding in front of frame 0
+    }
+    if (T1 > S->cap) {                 // grow in chunk multiples: at least twice the old capacity, never past max_frames; the rows held so far move over
+        const int cap = std::min(S->max_frames / ch * ch, std::max(T1, 2 * S->cap));
+        std::lock_guard<std::recursive_mutex> lk(runtime_lock());
+        void* nk = nullptr; const size_t bytes = nslab * cap * inner * esz;
+        CV_HIP(hipMalloc(&nk, bytes));
+        if (S->kv) {
+            hipError_t e = T0 > 0 ? hipMemcpy2DAsync(nk, (size_t)cap * inner * esz, S->kv, (size_t)S->cap * inner * esz, (size_t)T0 * inner * esz, nslab, hipMemcpyDeviceToDevice, s) : hipSuccess;
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) { (void)hipFree(nk); throw Error(std::string("cv_flow_stream_chunk: moving the caches: ") + hipGetErrorString(e)); }
+            (void)hipFree(S->kv);
+        }
+        m->stream_cache_bytes += (long long)bytes - (long long)S->kv_bytes;
+        S->kv = nk; S->kv_bytes = bytes; S->cap = cap;
+    }
+    // the front of cv_flow_inference(streaming = 1, finalize = 0) over ALL tokens (the encoder is a small share of a pass); only rows [T0, T1) of mu / cond are used
+    inf_reserve(m, n_tok, 1);
+    hipLaunchKernelGGL(l2_normalize_kernel, dim3(1), dim3(256), 0, s, embedding, m->f_spkn.as<float>(), c.spk_dim);
+    lin_cl(m->spk_affine, m->f_spkn.as<float>(), 1, m->f_spk.as<float>(), ACT_NONE, nullptr, s);
+    CV_CHECK(cv_gather_rows(m->input_embedding, m->wbf16 ? CV_BF16 : CV_F32, c.vocab, d, token_ids, n_tok, m->f_tok.as<float>(), 1.f, stream_r) == 0, cv_last_error());
+    flow_encoder(m, m->f_tok.as<float>(), n_enc, m->f_tok.as<float>() + (size_t)n_enc * d, 1, m->f_h.as<float>(), s);
+    lin_cl(m->enc_proj, m->f_h.as<float>(), T1, m->f_mu.as<float>(), ACT_NONE, nullptr, s);
+    const size_t per = (size_t)T1 * c.mel;
+    hipLaunchKernelGGL(copy_rows_zero_tail_kernel, dim3(nblk((long long)per)), dim3(256), 0, s, mel_len1 ? prompt_feat : m->f_cond.as<float>(), m->f_cond.as<float>(),
+                       (long long)mel_len1 * c.mel, (long long)per);
+    float* x = m->f_x.as<float>();
+    const long long n = (long long)Tn * c.mel;
+    CV_HIP(hipMemcpyAsync(x, noise_cl + (size_t)T0 * c.mel, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    est_reserve(m, Tn, 2); time_reserve(m, n_timesteps);
+    m->s_stg.ensure((size_t)2 * (Tn + 2) * Kmax * 4);
+    m->ac_m.ensure((size_t)2 * c.est_heads * Tn * 8 * 4); m->ac_l.ensure((size_t)2 * c.est_heads * Tn * 8 * 4); m->ac_o.ensure((size_t)2 * c.est_heads * Tn * 8 * 64 * 4);
+    std::vector<float> tv, dts;
+    euler_schedule(n_timesteps, tv, dts);
+    m->host_t = tv;
+    CV_HIP(hipMemcpyAsync(m->t_val.p, m->host_t.data(), (size_t)n_timesteps * 4, hipMemcpyHostToDevice, s));
+    time_embed(m, n_timesteps, s);
+    for (int st = 0; st < n_timesteps; ++st) {
+        hipLaunchKernelGGL(pack_est_input_kernel, dim3(nblk(2 * n * 4)), dim3(256), 0, s, x, m->f_mu.as<float>() + (size_t)T0 * c.mel, m->f_spk.as<float>(),
+                           m->f_cond.as<float>() + (size_t)T0 * c.mel, m->s_in.as<float>(), Tn, c.mel, 1, 1);
+        estimator_forward_inc(m, S, Tn, T0, st, s);
+        hipLaunchKernelGGL(cfg_euler_kernel, dim3(nblk(n)), dim3(256), 0, s, x, m->s_out.as<float>(), n, dts[st], c.cfg_rate);
+    }
+    const int t0 = first ? mel_len1 : 0;
+    hipLaunchKernelGGL(to_channel_first_kernel, dim3(nblk((long long)(Tn - t0) * c.mel)), dim3(256), 0, s, x, mel_out, 1, Tn, c.mel, t0, (const float*)nullptr);
+    CV_HIP(hipGetLastError());
+    *n_new = Tn - t0;
+    S->frames_done = T1; ++S->calls; ++m->stream_chunks;
+}
+
+int cv_flow_stream_open(cv_flow* m, int32_t max_frames, cv_flow_stream** out) {
+    return guarded([&] {
+        CV_CHECK(m && m->finalized && out, "cv_flow_stream_open: bad arguments");
+        CV_CHECK(m->cfg.estimator == 0, "cv_flow_stream_open: the incremental pass serves the causal U-Net estimator (cfg.estimator == 0) only, not the DiT or the CosyVoice-300M U-Net");
+        CV_CHECK(m->cfg.chunk > 0 && max_frames >= 2 * m->cfg.chunk, "cv_flow_stream_open: max_frames must hold at least one chunk");
+        auto* S = new cv_flow_stream(); S->owner = m; S->max_frames = max_frames; ++m->open_streams;
+        *out = S;
+    });
+}
+int cv_flow_stream_chunk(cv_flow* m, cv_flow_stream* st, const int32_t* token_ids, int32_t n_tok, const float* prompt_feat, int32_t mel_len1, const float* embedding,
+                         const float* noise_cl, int32_t n_timesteps, float* mel_out, int32_t* n_new, void* stream) {
+    return guarded([&] { flow_stream_chunk(m, st, token_ids, n_tok, prompt_feat, mel_len1, embedding, noise_cl, n_timesteps, mel_out, n_new, stream); });
+}
+int cv_flow_stream_slices(cv_flow* m, int32_t slices) {
+    return guarded([&] {
+        CV_CHECK(m, "cv_flow_stream_slices: null handle");
+        CV_CHECK(slices >= 0 && slices <= 8, "cv_flow_stream_slices: slices must be 0 .. 8 (got " + std::to_string(slices) + ")");
+        m->stream_slices = slices;
+    });
+}
+int cv_flow_stream_close(cv_flow* m, cv_flow_stream* st) {
+    return guarded([&] {
+        CV_CHECK(m && st, "cv_flow_stream_close: bad arguments");
+        CV_CHECK(st->owner == m, "cv_flow_stream_close: the stream was opened on another handle (or is closed)");
+        std::lock_guard<std::recursive_mutex> lk(runtime_lock());
+        (void)hipDeviceSynchronize();                     // launches of the last chunk may still read the caches
+        stream_release(st);
+        delete st;
+    });
+}
+int cv_flow_attention_cached(const void* q, int32_t ldq, const void* const* k, const void* const* v, const int32_t* klen, int32_t ldc, void* o, int32_t ldo,
+                             int32_t B, int32_t H, int32_t Tn, int32_t q0, int32_t chunk, float scale, int32_t slices, int32_t bf16, void* stream) {
+    return guarded([&] {
+        CV_CHECK(q && k && v && klen && o, "cv_flow_attention_cached: null operand");
+        CV_CHECK(B >= 1 && B <= ATTN_CACHED_MAX_B && H >= 1 && Tn >= 1 && q0 >= 0, "cv_flow_attention_cached: bad shape (1 <= B <= 8, H >= 1, Tn >= 1, q0 >= 0)");
+        const int vec = bf16 ? 8 : 4;
+        CV_CHECK(ldq % vec == 0 && ldq >= 64 * H && ldc % vec == 0 && ldc >= 64 * H, "cv_flow_attention_cached: bad ldq / ldc (a multiple of 16 bytes, at least 64 H)");
+        CV_CHECK(ldo % 4 == 0 && ldo >= 64 * H, "cv_flow_attention_cached: bad ldo (a multiple of 4, at least 64 H)");
+        CV_CHECK(aligned16(q) && (bf16 ? (reinterpret_cast<uintptr_t>(o) & 7) == 0 : aligned16(o)), "cv_flow_attention_cached: unaligned operand (16 B q, 16 B fp32 / 8 B bf16 o)");
+        CV_CHECK(std::isfinite(scale) && scale > 0.f, "cv_flow_attention_cached: bad scale (finite and positive)");
+        CV_CHECK(chunk >= 0, "cv_flow_attention_cached: bad chunk");
+        CV_CHECK(slices >= 1 && slices <= 8, "cv_flow_attention_cached: bad slices (1 .. 8)");
+        AttnCachedArgs a{};
+        for (int b = 0; b < B; ++b) {
+            CV_CHECK(klen[b] >= 0, "cv_flow_attention_cached: bad klen (>= 0)");
+            CV_CHECK(klen[b] == 0 || (k[b] && v[b] && aligned16(k[b]) && aligned16(v[b])), "cv_flow_attention_cached: null or unaligned cache base (16 B)");
+            a.k[b] = k[b]; a.v[b] = v[b]; a.klen[b] = klen[b];
+        }
+        hipStream_t s = as_stream(stream);
+        const size_t nq = (size_t)B * H * Tn;
+        DevBuf pm, pl, po;
+        if (slices > 1) { pm.ensure(nq * slices * 4); pl.ensure(nq * slices * 4); po.ensure(nq * slices * 64 * 4); }
+        a.q = q; a.ldq = ldq; a.ldc = ldc; a.o = o; a.ldo = ldo; a.pm = pm.as<float>(); a.pl = pl.as<float>(); a.po = po.as<float>();
+        a.B = B; a.H = H; a.Tn = Tn; a.q0 = q0; a.chunk = chunk; a.ns = slices; a.scale = scale;
+        attn_cached_launch(a, bf16 != 0, s);
+        CV_HIP(hipGetLastError());
+        CV_HIP(hipStreamSynchronize(s));                  // the partials are freed on return
     });
 }
 

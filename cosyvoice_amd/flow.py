@@ -172,6 +172,61 @@ class _Encoder(torch.nn.Module):
         return h, torch.ones(1, 1, 2 * n, dtype=torch.bool, device=f.device)
 
 
+class FlowStream:
+    """One streamed request on the incremental flow path (`CausalMaskedDiffWithXvec.open_stream`; cv_flow_stream_* in include/cosyvoice_amd.h).
+    `chunk(token, prompt_token, prompt_feat, embedding)` takes what `flow.inference(..., streaming=True, finalize=False)` takes - ALL tokens so far - and returns
+    only the mel frames this stream has not returned before, `[1, 80, n_new]`: the earlier chunks' transformer K / V rows and convolution halos are kept on the
+    device, so the Euler solve runs over the new frames alone.  The calls of one request must arrive chunk-aligned (`2 * (n_tok - pre_lookahead)` a multiple of
+    `2 * cfg.chunk`) with the same prompt; anything else raises CosyVoiceAmdError and leaves the stream as it was.  A context manager; `close()` frees the caches."""
+
+    def __init__(self, flow, max_frames):
+        self.flow, self.lib = flow, flow.lib
+        self._s = C.c_void_p()
+        self.lib.cv_flow_stream_open(flow._h, C.c_int32(int(max_frames)), C.byref(self._s))
+        self.frames_done = 0
+
+    @torch.inference_mode()
+    def chunk(self, token, prompt_token, prompt_feat, embedding):
+        f = self.flow
+        if not self._s:
+            raise ValueError("FlowStream.chunk: the stream is closed")
+        ids = f.lib.hook(torch.cat([prompt_token.reshape(-1).to(f.device, torch.int32), token.reshape(-1).to(f.device, torch.int32)]).clamp(min=0).contiguous())
+        n_tok = ids.numel()
+        pf = f.lib.hook(prompt_feat.to(f.device, torch.float32).contiguous())
+        mel_len1 = prompt_feat.shape[1]
+        emb = f.lib.hook(embedding.to(f.device, torch.float32).reshape(-1).contiguous())
+        T1 = 2 * (n_tok - f.pre_lookahead_len)
+        if T1 > f._noise_cl.shape[0]:
+            raise ValueError("%d mel frames exceed the fixed CFM noise buffer (%d frames = %d s)" % (T1, f._noise_cl.shape[0], f._noise_cl.shape[0] // 50))
+        n_max = max(T1 - (self.frames_done if self.frames_done else mel_len1), 1)
+        out = f.lib.hook(torch.empty(1, f.cfg.mel, n_max, dtype=torch.float32, device=f.device))
+        got = C.c_int32(0)
+        f.lib.cv_flow_stream_chunk(f._h, self._s, C.c_void_p(ids.data_ptr()), C.c_int32(n_tok), C.c_void_p(pf.data_ptr()) if mel_len1 else None, C.c_int32(mel_len1),
+                                   C.c_void_p(emb.data_ptr()), C.c_void_p(f._noise_cl.data_ptr()), C.c_int32(f.n_timesteps), C.c_void_p(out.data_ptr()), C.byref(got),
+                                   stream_ptr(f.lib))
+        assert got.value == n_max
+        self.frames_done = T1
+        return out
+
+    def close(self):
+        if getattr(self, "_s", None):
+            s, self._s = self._s, None
+            self.lib.cv_flow_stream_close(self.flow._h, s)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _CFM:
     def __init__(self, flow):
         self.estimator = _Estimator(flow)
@@ -227,6 +282,16 @@ class CausalMaskedDiffWithXvec:
         busy: p50 101.5 vs 104.9 ms) - so CosyVoice2Model asks for 1 and StreamScheduler for 3000 while it runs (profiles/r6_flow_graph_threshold.txt)."""
         self._graph_rows = int(n)
         self.lib.cv_flow_set_option(self._h, b"graph_max_rows", C.c_int32(int(n)))
+
+    def open_stream(self, max_frames=None):
+        """The incremental streaming path for ONE request (`FlowStream`): `max_frames` caps the frames (prompt included) its device caches may grow to; the default
+        is the fixed CFM noise buffer's length, the most any request can reach."""
+        return FlowStream(self, self._noise_cl.shape[0] if max_frames is None else max_frames)
+
+    def stat(self, name):
+        v = C.c_int64(0)
+        self.lib.cv_flow_get_stat(self._h, name.encode(), C.byref(v))
+        return v.value
 
     def __del__(self):
         try:

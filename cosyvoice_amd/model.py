@@ -89,6 +89,13 @@ class CosyVoice2Model:
         # ... and, opt-in until measured on the MI355X (bench.py --hift-batch / CV_HIFT_BATCH=1), the equal-length members of such a group share ONE HiFT launch
         # sequence as well (HiFTGenerator.inference_batch; bit-identical per utterance)
         self.hift_batch = os.environ.get("CV_HIFT_BATCH", "0") == "1"
+        # Opt-in (CV_FLOW_INCREMENTAL=1): the streaming chunks of a request - token2wav(stream=True, finalize=False) - keep ONE incremental flow stream per uuid
+        # (flow.open_stream: the Euler solve runs over the new frames only, against cached K / V rows and convolution halos) instead of re-solving all frames at every
+        # hop.  The final call of a request (finalize=True: a full, non-chunked pass whose prefix sees future frames) stays on the existing pass.  Measured in
+        # profiles/flow_incremental.txt; off by default.
+        self.flow_incremental = os.environ.get("CV_FLOW_INCREMENTAL", "0") == "1"
+        self._flow_streams = {}                # uuid -> (flow instance that opened it, FlowStream), or False once the request has fallen back to the existing pass
+        self.flow_passes = {"incremental": 0, "full": 0}          # flow passes of token2wav by path (monitoring / tests)
         self.set_lanes(1)
         self.tts_speech_token_dict, self.llm_end_dict, self.hift_cache_dict, self._cond = {}, {}, {}, {}
         self._llm_error = {}                   # uuid -> exception raised on the LLM thread, re-raised by tts() on the caller's thread
@@ -249,10 +256,51 @@ class CosyVoice2Model:
     def token2wav(self, token, prompt_token, prompt_feat, embedding, token_offset, uuid, stream=False, finalize=False, speed=1.0):
         """cli/model.py:292-326."""
         with self._lane() as lane:
+            if self.flow_incremental and stream is True and finalize is False and speed == 1.0:
+                inc = self._flow_chunk_incremental(lane, token, prompt_token, prompt_feat, embedding, token_offset, uuid)
+                if inc is not None:
+                    return self._t2w_tail(lane, inc[0], token, token_offset, uuid, finalize, speed, mel_offset=inc[1])
+            elif finalize:
+                self._close_flow_stream(uuid)                             # the last call of a streamed request: a full pass, the caches are done with
             t = lambda n: torch.tensor([n], dtype=torch.int32)
             tts_mel, _ = lane.flow.inference(token=token.to(torch.int32), token_len=t(token.shape[1]), prompt_token=prompt_token, prompt_token_len=t(prompt_token.shape[1]),
                                              prompt_feat=prompt_feat, prompt_feat_len=t(prompt_feat.shape[1]), embedding=embedding, streaming=stream, finalize=finalize)
+            self.flow_passes["full"] += 1
             return self._t2w_tail(lane, tts_mel, token, token_offset, uuid, finalize, speed)
+
+    def _flow_chunk_incremental(self, lane, token, prompt_token, prompt_feat, embedding, token_offset, uuid):
+        """The new mel frames of a streaming chunk from the request's incremental flow stream -> (mel [1, 80, n_new], frames of it that lie before the slice
+        `_t2w_tail` takes), or None: the caller runs the existing pass, and so does every later chunk of the request.  That happens when the lane's flow cannot open a
+        stream (a DiT), is another clone than the one that opened the request's stream, or the library refuses the call (a chunk that is not aligned)."""
+        from ._lib import CosyVoiceAmdError
+        flow = lane.flow
+        ent = self._flow_streams.get(uuid)
+        if ent is False or not hasattr(flow, "open_stream") or flow.cfg.estimator == "dit":
+            return None
+        if ent is not None and ent[0] is not flow:
+            self._close_flow_stream(uuid, fell_back=True)
+            return None
+        try:
+            if ent is None:
+                ent = self._flow_streams[uuid] = (flow, flow.open_stream())
+            first = ent[1].frames_done or prompt_feat.shape[1]            # absolute frame the returned mel starts at
+            mel = ent[1].chunk(token.to(torch.int32), prompt_token, prompt_feat, embedding)
+        except CosyVoiceAmdError:
+            self._close_flow_stream(uuid, fell_back=True)
+            return None
+        skip = prompt_feat.shape[1] + token_offset * flow.token_mel_ratio - first
+        if skip < 0:                                                      # (prompt_feat longer than 2 x prompt tokens: frames of this slice went out with an earlier call)
+            self._close_flow_stream(uuid, fell_back=True)
+            return None
+        self.flow_passes["incremental"] += 1
+        return mel, skip
+
+    def _close_flow_stream(self, uuid, fell_back=False):
+        ent = self._flow_streams.pop(uuid, None)
+        if ent:
+            ent[1].close()
+        if fell_back:
+            self._flow_streams[uuid] = False
 
     @torch.inference_mode()
     def token2wav_batch(self, jobs, stream=False, finalize=False, on_ready=None):
@@ -279,10 +327,11 @@ class CosyVoice2Model:
                     on_ready(i, outs[-1])
             return outs
 
-    def _t2w_tail(self, lane, tts_mel, token, token_offset, uuid, finalize, speed):
-        """Everything of token2wav after the flow (cli/model.py:301-326): new frames -> mel / source caches -> HiFT -> fade."""
+    def _t2w_tail(self, lane, tts_mel, token, token_offset, uuid, finalize, speed, mel_offset=None):
+        """Everything of token2wav after the flow (cli/model.py:301-326): new frames -> mel / source caches -> HiFT -> fade.
+        mel_offset: where the new frames start in tts_mel when it is not the whole mel of the request (the incremental flow path)."""
         flow, hift = lane.flow, lane.hift
-        tts_mel = tts_mel[:, :, token_offset * flow.token_mel_ratio:]
+        tts_mel = tts_mel[:, :, token_offset * flow.token_mel_ratio if mel_offset is None else mel_offset:]
         cache = self.hift_cache_dict.get(uuid)
         if cache is not None:
             tts_mel = torch.concat([cache["mel"], tts_mel], dim=2)
@@ -568,6 +617,8 @@ class CosyVoice2Model:
                 self.hift_cache_dict.pop(this_uuid, None)
                 self._cond.pop(this_uuid, None)
                 self._llm_error.pop(this_uuid, None)
+            self._close_flow_stream(this_uuid)
+            self._flow_streams.pop(this_uuid, None)
 
 
 class CosyVoice3Model(CosyVoice2Model):

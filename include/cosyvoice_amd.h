@@ -211,7 +211,8 @@ int cv_flow_finalize(cv_flow* m);
  * bit-identical per utterance.  Round 6: "ln_qkv" (1), "attn32_waves" (0 = 4 | 2 | 4: 128- or 64-query workgroups of the flash attention), "res_tile" (1: the
  * small-pass residual GEMMs on 32 x 32 tiles, 0: 32 x 64). */
 int cv_flow_set_option(cv_flow* m, const char* name, int32_t value);
-/* "graph_captures" (Euler-solve graphs captured so far), "graphs_cached" (held now; option "graph_cap", default 32) - test / monitoring hook, no reference counterpart */
+/* "graph_captures" (Euler-solve graphs captured so far), "graphs_cached" (held now; option "graph_cap", default 32), "stream_cache_bytes" (device bytes held by the open
+ * cv_flow_streams), "stream_chunks" (cv_flow_stream_chunk calls served), "open_streams" - test / monitoring hook, no reference counterpart */
 int cv_flow_get_stat(cv_flow* m, const char* name, int64_t* value);
 void cv_flow_destroy(cv_flow* m);
 /* measurement hook (bench.py `roofline_mfma`; no reference counterpart): the QKV GEMM, the flash attention and the 64-row band launch (csrc/flow_band.h) of one transformer
@@ -280,6 +281,37 @@ int cv_flow_inference_ragged(cv_flow* m, int32_t n_utt, const int32_t* token_ids
                              int32_t* mel_len2_out, void* stream);
 int cv_flow_inference_batch(cv_flow* m, int32_t n_utt, const int32_t* token_ids, int32_t n_tok, const float* prompt_feat, int32_t mel_len1, const float* embedding,
                             const float* noise_cl, int32_t streaming, int32_t finalize, int32_t n_timesteps, float* mel_out, int32_t* mel_len2_out, void* stream);
+/* Incremental streaming flow (opt-in; no reference counterpart: CosyVoice2Model.token2wav, cli/model.py:292-303, re-runs flow.inference over ALL tokens at every hop
+ * and keeps the tail).  With streaming = 1 the estimator is chunk-causal, so the frames of an arriving chunk need from the earlier ones only the K / V rows of every
+ * transformer block and the two rows in front of every kernel-3 convolution, per Euler step and guidance row: a cv_flow_stream holds them for ONE request.
+ * cv_flow_stream_open stands in for nothing in the reference; max_frames caps the frames (2 per token, prompt included) the stream's caches may grow to - they cost
+ * 2 * 64 est_heads * (4 | 2 bytes) per frame, transformer block, Euler step and guidance row, allocated in chunk multiples as the request grows.  Causal U-Net
+ * estimator (cfg.estimator == 0) only.  The state belongs to the stream: several streams may be open on one handle and do not see each other; calls on one handle
+ * are serialised by the caller, as for every other entry point.  Close every stream before cv_flow_destroy. */
+typedef struct cv_flow_stream cv_flow_stream;
+int cv_flow_stream_open(cv_flow* m, int32_t max_frames, cv_flow_stream** out);
+/* = cv_flow_inference(streaming = 1, finalize = 0) on the same arguments (flow/flow.py:235-281 + flow_matching.py:71-124,203-227), except that it returns only the
+ * frames this stream has not returned before: [mel_len1, T1) on the first call, [frames_done, T1) later, T1 = 2 (n_tok - pre_lookahead); mel_out dev [80][*n_new].
+ * The first call is a full pass that fills the caches; later calls run the encoder over all tokens and the Euler solve over the new frames only.  Not captured as a
+ * hipGraph.  Refused with a message that names this entry point: T1 not a multiple of the 2 cfg.chunk-frame chunk, T1 <= frames_done (no new chunk), T1 > max_frames,
+ * mel_len1 / n_timesteps / the precision mode other than on the stream's first call, a stream of another handle, bf16 mode without the fused pipeline.  A refused call
+ * leaves the stream as it was. */
+int cv_flow_stream_chunk(cv_flow* m, cv_flow_stream* st, const int32_t* token_ids, int32_t n_tok, const float* prompt_feat, int32_t mel_len1, const float* embedding,
+                         const float* noise_cl, int32_t n_timesteps, float* mel_out, int32_t* n_new, void* stream);
+/* measurement / test hook: key slices of the cached attention (csrc/flow_attn_cached.h) for the chunks this handle serves from now on - 1 .. 8, or 0 (the default): by
+ * the key count of the call (csrc/flow.hip stream_slices_for, measured in profiles/flow_incremental.txt).  A query's bits depend on the slice count. */
+int cv_flow_stream_slices(cv_flow* m, int32_t slices);
+/* frees the stream's caches (cv_flow_get_stat "stream_cache_bytes" goes back by their size); waits for the device first */
+int cv_flow_stream_close(cv_flow* m, cv_flow_stream* st);
+/* test hook (no reference counterpart): the attention of the incremental pass (csrc/flow_attn_cached.h), launched exactly as cv_flow_stream_chunk launches it.
+ * q: dev [B][Tn][ldq], the new queries at absolute positions q0 .. q0 + Tn - 1, head h at columns [64 h, 64 h + 64); k, v: HOST arrays [B] of dev cache bases, rows
+ * [klen[b]][ldc]; klen: HOST int32 [B]; o: dev [B][Tn][ldo].  Query i of batch row b sees keys < min(klen[b], ((q0 + i) / chunk + 1) chunk) (chunk = 0: < klen[b]); none
+ * visible: a zero row.  bf16 = 0: fp32 q / k / v / o; 1: bf16 q / k / v / o with P rounded to bf16 and fp32 accumulation.  slices: 1 .. 8 key slices (a query's bits depend
+ * on its position, klen, chunk and slices alone).  Cache rows at or beyond klen[b] are never read.  Refused with a message: null operands, B outside 1 .. 8, H / Tn < 1,
+ * q0 < 0, leading dimensions below 64 H or not a multiple of 16 bytes (ldo: of 4 elements), unaligned bases, scale not finite and positive, chunk < 0, slices outside
+ * 1 .. 8, klen < 0.  Synchronises `stream` before it returns. */
+int cv_flow_attention_cached(const void* q, int32_t ldq, const void* const* k, const void* const* v, const int32_t* klen, int32_t ldc, void* o, int32_t ldo,
+                             int32_t B, int32_t H, int32_t Tn, int32_t q0, int32_t chunk, float scale, int32_t slices, int32_t bf16, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Stage B6 — HiFT vocoder.  Weight names: cosyvoice_amd/weights.py:pack_hift (weight-norm folded, fp32).
