@@ -406,6 +406,38 @@ int cv_hift_inference_batch(cv_hift* m, int32_t n_utt, const float* speech_feat,
     });
 }
 
+/* Kernel-test entry points (tests/test_hift_kernels.py): the launches of hift_source / hift_decode / hift_decode_causal without the convolution stack. */
+int cv_hift_source(cv_hift* m, const float* f0, int32_t frames, const float* noise, uint64_t seed, float* phase_out, float* source_out, void* stream) {
+    return guarded([&] {
+        CV_CHECK(m && m->finalized && f0 && source_out && frames > 0, "cv_hift_source: bad arguments");
+        hipStream_t s = as_stream(stream);
+        reserve(m, frames);
+        const long long L = (long long)frames * m->scale;
+        CV_HIP(hipMemcpyAsync(m->f0.p, f0, (size_t)frames * 4, hipMemcpyDeviceToDevice, s));
+        hift_source(m, frames, noise, seed, s);
+        if (phase_out) CV_HIP(hipMemcpyAsync(phase_out, m->P.p, (size_t)frames * (m->cfg.harmonics + 1) * 4, hipMemcpyDeviceToDevice, s));
+        CV_HIP(hipMemcpyAsync(source_out, m->s.p, (size_t)L * 4, hipMemcpyDeviceToDevice, s));
+    });
+}
+int cv_hift_stft(const float* source, int64_t L, float* out, void* stream) {
+    return guarded([&] {
+        CV_CHECK(source && out, "cv_hift_stft: null argument");
+        CV_CHECK(L >= 16 && L % 4 == 0, "cv_hift_stft: L must be a multiple of 4 (the hop) and at least 16 (the reflection reads 8 samples past either end)");
+        const long long F = L / 4 + 1;
+        hipLaunchKernelGGL(hift_stft_kernel, dim3(nblk(F)), dim3(256), 0, as_stream(stream), source, out, (long long)L, F);
+    });
+}
+int cv_hift_istft(float* spec, int64_t F, int64_t L, float limit, float* speech_out, void* stream) {
+    return guarded([&] {
+        CV_CHECK(spec && speech_out, "cv_hift_istft: null argument");
+        CV_CHECK(F >= 2 && L > 0 && L <= 4 * (F - 1), "cv_hift_istft: F >= 2 frames give at most 4 (F - 1) samples");
+        CV_CHECK(limit > 0.f, "cv_hift_istft: bad limit (positive)");
+        hipStream_t s = as_stream(stream);
+        hipLaunchKernelGGL(hift_spec_kernel, dim3(nblk(F * 9)), dim3(256), 0, s, spec, (long long)F);
+        hipLaunchKernelGGL(hift_istft_kernel, dim3(nblk(L)), dim3(256), 0, s, spec, speech_out, (long long)F, (long long)L, limit);
+    });
+}
+
 /* CausalHiFTGenerator (Fun-CosyVoice3) entry points; the handle must have been created with cfg.causal = 1. */
 int cv_hift_causal_f0(cv_hift* m, const float* speech_feat, int32_t frames, int32_t finalize, float* f0_out, int32_t* n_out, void* stream) {
     return guarded([&] {

@@ -23,6 +23,9 @@ static __global__ __launch_bounds__(256) void to_channel_last_kernel(const float
 // The walk stays sequential per harmonic (the summation order is part of the result: the phase reaches thousands of radians); what is parallel is
 // everything around it: f0 is fetched in coalesced chunks and the per-frame increment ((f0 * (h + 1)) / sr) mod 1 - the expensive part, fmodf - is
 // computed by all 256 threads into LDS, so the serial loop is one add and one store per frame (65 us -> a few us for 500 frames).
+// The running sum c is carried from chunk to chunk and `rad` is reused behind the two barriers: utterances over 512 frames (10.24 s) take the second
+// iteration.  Pinned bit for bit against a sequential fp32 sum at 1 .. 1537 frames by tests/test_hift_kernels.py::test_phase_walk_equals_the_sequential_fp32_sum_bit_for_bit
+// (and, through the source, by ::test_source_against_the_oracle_on_the_same_f0 at 513 and 1025 frames).
 static __global__ __launch_bounds__(256) void hift_phase_kernel(const float* f0, float* P, int m, int H, float sr, float scale) {
     constexpr int CH = 512;                                   // frames per chunk; H <= 16 harmonics
     __shared__ float rad[CH * 16];

@@ -361,6 +361,20 @@ int cv_hift_causal_decode(cv_hift* m, const float* speech_feat, int32_t frames, 
                           void* stream);
 int cv_hift_causal_inference(cv_hift* m, const float* speech_feat, int32_t frames, int32_t finalize, const float* noise, uint64_t seed,
                              float* speech_out, int64_t* n_speech, float* source_out, int64_t* n_source, void* stream);
+/* test hooks (no reference counterpart): the vocoder's element kernels (csrc/hift_kernels.h) launched exactly as the entry points above launch them, without the
+ * f0 predictor and the convolution stack.
+ * cv_hift_source: the phase walk + the source kernel of cv_hift_inference / cv_hift_causal_inference on a GIVEN f0: f0 dev [frames] (copied into the handle's f0
+ *   buffer), noise dev [480 frames, 9] or NULL -> counter RNG keyed by `seed`; the handle's cfg.causal selects nearest / linear phase upsampling and uniform / Gaussian
+ *   noise.  phase_out: dev [frames][harmonics + 1], the low-rate phase P, or NULL; source_out: dev [480 frames].
+ * cv_hift_stft: source dev [L] -> out dev [L / 4 + 1][18] = (re(9) | im(9)) of torch.stft(16, 4, 16, hann, center, reflect); L a multiple of 4, at least 16.
+ * cv_hift_istft: spec dev [F][18], the conv_post output - OVERWRITTEN with the complex spectrum (min(exp, 100), sin -> polar form), as in production - then
+ *   torch.istft(16, 4, 16, hann) clamped to +-limit: the first L <= 4 (F - 1) samples -> speech_out dev [L] (L < 4 (F - 1): a non-final causal chunk, whose tail
+ *   is withheld).
+ * Refused with a message: null operands (but noise / phase_out), an unfinalized handle, frames < 1, L not a multiple of 4 or below 16 (stft), F < 2, L < 1 or
+ * L > 4 (F - 1), limit not positive (istft). */
+int cv_hift_source(cv_hift* m, const float* f0, int32_t frames, const float* noise, uint64_t seed, float* phase_out, float* source_out, void* stream);
+int cv_hift_stft(const float* source, int64_t L, float* out, void* stream);
+int cv_hift_istft(float* spec, int64_t F, int64_t L, float limit, float* speech_out, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------------------

@@ -40,15 +40,27 @@ def f0_predictor(sd, mel):
     return torch.abs(F.linear(x.transpose(1, 2), sd["f0_predictor.classifier.weight"], sd["f0_predictor.classifier.bias"]).squeeze(-1))
 
 
-def sine_gen2(cfg, f0, rand_ini, noise):
-    """SineGen2.forward: f0 [1,L,1] (already upsampled), rand_ini [1,9] (col 0 = 0), noise [1,L,9] ~ N(0,1)."""
+def cumsum_fp32(x, dim=1):
+    """torch.cumsum(x, dim) of an fp32 tensor with an FP32 running sum in index order.  torch's CPU kernel accumulates fp32 inputs in DOUBLE and rounds every
+    output once; the reference runs on the device, where the accumulator is fp32 like the values.  Over a thousand frames the two differ by tens of ulp of the
+    sum - 0.1 rad of harmonic phase after 1025 frames.  The kernel tests (tests/test_hift_kernels.py) pass this as `cumsum` so that the phase is the fp32 value."""
+    x = x.transpose(dim, 0).contiguous().numpy().astype(np.float32)
+    out, acc = np.empty_like(x), np.zeros(x.shape[1:], np.float32)
+    for i in range(x.shape[0]):
+        acc = acc + x[i]
+        out[i] = acc
+    return torch.from_numpy(out).transpose(dim, 0)
+
+
+def sine_gen2(cfg, f0, rand_ini, noise, cumsum=torch.cumsum):
+    """SineGen2.forward: f0 [1,L,1] (already upsampled), rand_ini [1,9] (col 0 = 0), noise [1,L,9] ~ N(0,1).  cumsum: torch.cumsum or cumsum_fp32."""
     H = cfg.harmonics + 1
     scale = int(np.prod(cfg.ups) * cfg.hop)
     fn = f0 * torch.arange(1, H + 1, dtype=torch.float32).reshape(1, 1, H)
     rad = (fn / cfg.sr) % 1
     rad[:, 0, :] = rad[:, 0, :] + rand_ini
     rad = F.interpolate(rad.transpose(1, 2), scale_factor=1 / scale, mode="linear").transpose(1, 2)
-    phase = torch.cumsum(rad, dim=1) * 2 * np.pi
+    phase = cumsum(rad, dim=1) * 2 * np.pi
     phase = F.interpolate(phase.transpose(1, 2) * scale, scale_factor=scale, mode="linear").transpose(1, 2)
     sines = torch.sin(phase) * cfg.nsf_alpha
     uv = (f0 > cfg.voiced_thr).float()
@@ -152,15 +164,16 @@ def causal_f0_predictor(sd, mel, finalize=True, dtype=torch.float64):
     return torch.abs(F.linear(x.transpose(1, 2), sd["f0_predictor.classifier.weight"].to(dtype), sd["f0_predictor.classifier.bias"].to(dtype)).squeeze(-1)).float()
 
 
-def causal_sine_gen2(cfg, f0, rand_ini, noise):
-    """SineGen2 with causal=True in eval mode (generator.py:233-258, 289-317): fixed rand_ini / uniform noise buffers, NEAREST phase upsampling."""
+def causal_sine_gen2(cfg, f0, rand_ini, noise, cumsum=torch.cumsum):
+    """SineGen2 with causal=True in eval mode (generator.py:233-258, 289-317): fixed rand_ini / uniform noise buffers, NEAREST phase upsampling.
+    cumsum: as in sine_gen2."""
     H = cfg.harmonics + 1
     scale = int(np.prod(cfg.ups) * cfg.hop)
     fn = f0 * torch.arange(1, H + 1, dtype=torch.float32).reshape(1, 1, H)
     rad = (fn / cfg.sr) % 1
     rad[:, 0, :] = rad[:, 0, :] + rand_ini
     rad = F.interpolate(rad.transpose(1, 2), scale_factor=1 / scale, mode="linear").transpose(1, 2)
-    phase = torch.cumsum(rad, dim=1) * 2 * np.pi
+    phase = cumsum(rad, dim=1) * 2 * np.pi
     phase = F.interpolate(phase.transpose(1, 2) * scale, scale_factor=scale, mode="nearest").transpose(1, 2)
     sines = torch.sin(phase) * cfg.nsf_alpha
     uv = (f0 > cfg.voiced_thr).float()

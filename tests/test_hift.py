@@ -47,7 +47,8 @@ def test_decode_vs_oracle(lib, tiny):
 
 
 def test_source_statistics_with_device_rng(lib, tiny):
-    """Without the parity hook the SineGen2 noise comes from the in-kernel RNG: same f0, same deterministic part, noise ~ N(0,1)."""
+    """Without the parity hook the SineGen2 noise comes from the in-kernel RNG: same f0, same deterministic part, noise ~ N(0,1).
+    The distribution itself (moments, tails, independent streams per harmonic and seed) is checked in tests/test_hift_kernels.py::test_counter_rng_*."""
     cfg, sd = tiny
     hift = HiFTGenerator(sd, cfg, lib=lib)
     gen = torch.Generator().manual_seed(6)

@@ -301,7 +301,8 @@ def test_flow_inference_u10(lib):
 
 def test_hift_u10(lib):
     """HiFT on the benchmark's 500 frames: f0 -> source -> decode with the oracle's source fed to both decoders (the source integrates f0
-    into a phase of thousands of radians, so it is compared separately at the tolerance of the tiny tests)."""
+    into a phase of thousands of radians, so it is compared separately at the tolerance of the tiny tests).  The source kernels themselves are bounded
+    separately on a shared f0 in tests/test_hift_kernels.py, so what remains in the 2.5e-2 below is the f0 predictor's rounding."""
     hc = _cfgs(lib)[2]
     sd = W.make_hift(hc)
     hift = HiFTGenerator(sd, hc, lib=lib)
